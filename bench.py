@@ -14,6 +14,18 @@ Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W
   # N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
   #        --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline figure needs: build the graph, warm
+up, time the K steps, print one JSON result line.
+
+  --dump-outputs DIR  after the timed steps, write the per-vertex results of
+                      the suite (BFS depth, SSSP distance, PageRank rank) as
+                      DIR/<name>.npy (float64), indexed by a fixed seeded
+                      sample of vertex ids (DIR/sample_oids.npy), so two
+                      builds can be compared output for output.
+  --full              reserved for measurements beyond the headline figure
+                      (baselines, other sizes or precisions). The benchmark
+                      has none today, so the flag changes nothing yet.
 """
 import argparse
 import json
@@ -33,6 +45,56 @@ DATAGEN_9_0_FB_E = 1_010_447_118
 BASELINE_SUITE_TEPS = 12.0 * DATAGEN_9_0_FB_E / (0.07 + 0.42 + 1.40)
 
 
+# --dump-outputs: vertices sampled per run (3 float64 arrays + the ids stay
+# far below the 64 MB cap: 4 x 8 MB)
+DUMP_SAMPLE = 1 << 20
+
+
+def dump_outputs(outdir, eng, g, args, rank, world):
+    """Write what the suite computes on the resident graph.
+
+    The timed calls run with values=False: results stay on the device and
+    the caller receives only counters. The same three calls are repeated
+    here, untimed, with values=True, i.e. the arrays a caller of the suite
+    receives. Rows come back in the engine's internal (hub-renumbered)
+    order, so they are indexed by original vertex id: DIR/<name>.npy[i] is
+    the value of vertex DIR/sample_oids.npy[i]. The sample depends only on
+    --seed and --nv. With several ranks each writes the sampled vertices it
+    owns, as <name>_rank<r>.npy.
+    """
+    import numpy as np
+
+    if args.nv <= DUMP_SAMPLE:
+        sample = np.arange(args.nv, dtype=np.int64)
+    else:
+        rng = np.random.default_rng(args.seed)
+        sample = np.unique(rng.integers(0, args.nv, DUMP_SAMPLE))
+    wanted = np.zeros(args.nv, dtype=bool)
+    wanted[sample] = True
+
+    os.makedirs(outdir, exist_ok=True)
+    suffix = "" if world == 1 else "_rank%d" % rank
+    rows = None
+    for name, run in (
+            ("bfs", lambda: eng.bfs(g, args.source)),
+            ("sssp", lambda: eng.sssp(g, args.source)),
+            ("pagerank", lambda: eng.pagerank(g, 0.85, args.pr_iters))):
+        r = run()
+        if rows is None:
+            # same graph, same row order for all three results
+            oids = r["oids"]
+            rows = np.nonzero(wanted[oids])[0]
+            mine = oids[rows]
+            order = np.argsort(mine, kind="stable")
+            rows, mine = rows[order], mine[order]
+            np.save(os.path.join(outdir, "sample_oids%s.npy" % suffix),
+                    mine.astype(np.float64))
+            del oids
+        np.save(os.path.join(outdir, name + suffix + ".npy"),
+                np.asarray(r["values"])[rows].astype(np.float64))
+        del r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -43,7 +105,15 @@ def main():
     ap.add_argument("--nv", type=int, default=DATAGEN_9_0_FB_V)
     ap.add_argument("--ne", type=int, default=DATAGEN_9_0_FB_E)
     ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the suite's per-vertex results (seeded "
+                         "vertex sample) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (none today)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     import grapehip
 
@@ -92,6 +162,9 @@ def main():
     elapsed = eng.allreduce_max(t1 - t0)
     teps = traversed_total / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, g, args, rank, world)
 
     if rank == 0:
         out = {

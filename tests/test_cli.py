@@ -9,11 +9,10 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-REPO = Path(__file__).resolve().parent.parent
-DATASET = Path("/root/reference/dataset")
+from golden_data import p2p31_dir
 
-pytestmark = pytest.mark.skipif(
-    not DATASET.exists(), reason="reference dataset not available")
+REPO = Path(__file__).resolve().parent.parent
+DATASET = p2p31_dir()
 
 
 def run_cli(tmp_path, *extra):

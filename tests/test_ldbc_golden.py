@@ -1,20 +1,15 @@
 """Parity check against LDBC golden outputs of the reference's bundled
-p2p-31 dataset (runs only where /root/reference is mounted; skipped
-elsewhere, e.g. on GPU boxes). Validates BFS/SSSP/PR/WCC/CDLP/LCC end to end
-on a real LDBC-format input including the .v/.e loaders."""
-import os
-from pathlib import Path
-
+p2p-31 dataset (stored under tests/golden/p2p-31). Validates
+BFS/SSSP/PR/WCC/CDLP/LCC end to end on a real LDBC-format input including
+the .v/.e loaders."""
 import numpy as np
 import pytest
 
 import grapehip
+from golden_data import p2p31_dir
 from grapehip.io import read_ldbc_edges, read_ldbc_vertices
 
-DATASET = Path("/root/reference/dataset")
-
-pytestmark = pytest.mark.skipif(
-    not DATASET.exists(), reason="reference dataset not available")
+DATASET = p2p31_dir()
 
 
 def load_golden(name):

@@ -1079,10 +1079,20 @@ __global__ void pr_apply_kernel(double* __restrict__ rank,
 // and the out-degree offsets instead of three (apply, then contrib, then
 // dangling each re-reading rank). Single-GPU pull path; rows beyond
 // owned_real (hashmap padding) get the rank update only.
+//
+// Only the active rows (rows_active: an edge in the pull or the out-CSR)
+// are visited. An isolated row's acc is 0, so its rank is exactly `base`
+// every iteration: the whole isolated population is carried by scalars.
+// Thread 0 of block 0 adds n_isolated * base to the next dangling sum and
+// n_isolated * |base - previous base| to the L1 delta, then stores base in
+// *prev_base (read and written by that thread alone; the first iteration
+// finds 1/N there). pr_fill_isolated_kernel writes the last base into
+// the isolated rows' ranks after the loop.
 __global__ void pr_fused_apply_kernel(
     double* __restrict__ rank, const double* __restrict__ acc,
     const double* __restrict__ dangling_cur, double inv_n, double damping,
-    uint32_t v_begin, uint32_t owned, uint32_t owned_real,
+    uint32_t v_begin, const uint32_t* __restrict__ rows, uint64_t nrows,
+    uint32_t owned_real, double n_isolated, double* __restrict__ prev_base,
     const uint64_t* __restrict__ off, float* __restrict__ contrib,
     double* __restrict__ dangling_next, double* __restrict__ l1_delta) {
   __shared__ double s_wave[kBlock / kWave];
@@ -1091,8 +1101,10 @@ __global__ void pr_fused_apply_kernel(
       (1.0 - damping) * inv_n + damping * (*dangling_cur) * inv_n;
   double d1 = 0, dang = 0;
   size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < owned;
-       r += stride) {
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < nrows; i += stride) {
+    uint32_t r = rows[i];
     double nv = base + damping * acc[v_begin + r];
     if (l1_delta) d1 += fabs(nv - rank[v_begin + r]);
     rank[v_begin + r] = nv;
@@ -1105,6 +1117,11 @@ __global__ void pr_fused_apply_kernel(
         dang += nv;
       }
     }
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    dang += n_isolated * base;
+    if (l1_delta) d1 += n_isolated * fabs(base - *prev_base);
+    *prev_base = base;
   }
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {
@@ -1295,7 +1312,8 @@ namespace grapehip {
 // (or the in-CSR for directed graphs) every owned row's full neighborhood is
 // local, so each row's accumulator is a private sum — the fp64-atomic push
 // was 10x slower at datagen-9_0 scale. Rows are bucketed by degree once:
-// thread-per-row (<64), wave-per-row (<16384), block-per-row (rest) — the
+// thread-per-row (1..63), wave-per-row (<16384), block per 4096-arc segment
+// (rest); rows without a pull edge are in no bucket — the
 // preprocessed analogue of the reference's CTA scheduler
 // (cuda/parallel/parallel_engine.h LBCTA :849-879).
 // ===========================================================================
@@ -1305,37 +1323,100 @@ constexpr uint64_t kMidDeg = 16384;
 
 // Block-aggregated: LDS tallies + one global reservation per block per
 // bucket (405M per-thread global atomics on 3 hot words took 4.8 s).
+//
+// Rows with no pull edge go into no list. Those that have no out-edge
+// either (out_off == off for undirected graphs) are isolated and only
+// counted: cnt[3] for real rows, cnt[4] for padding rows >= owned_real.
+// cnt[0..2] are the small/mid/large list lengths.
+__device__ __forceinline__ bool row_has_edges(
+    const uint64_t* __restrict__ off, const uint64_t* __restrict__ out_off,
+    uint32_t r) {
+  return off[r + 1] != off[r] || out_off[r + 1] != out_off[r];
+}
+
 __global__ void bucket_rows_kernel(const uint64_t* __restrict__ off,
-                                   uint32_t owned, uint32_t* sm,
-                                   unsigned long long* cs, uint32_t* md,
-                                   unsigned long long* cm, uint32_t* lg,
-                                   unsigned long long* cl) {
-  __shared__ uint32_t s_cnt[3];
+                                   const uint64_t* __restrict__ out_off,
+                                   uint32_t owned, uint32_t owned_real,
+                                   uint32_t* sm, uint32_t* md, uint32_t* lg,
+                                   unsigned long long* cnt) {
+  __shared__ uint32_t s_cnt[5];
   __shared__ unsigned long long s_base[3];
   uint32_t* lists[3] = {sm, md, lg};
-  unsigned long long* gcnt[3] = {cs, cm, cl};
   const uint32_t stride = gridDim.x * blockDim.x;
   for (uint32_t base = blockIdx.x * blockDim.x; base < owned;
        base += stride) {
-    if (threadIdx.x < 3) s_cnt[threadIdx.x] = 0;
+    if (threadIdx.x < 5) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     uint32_t r = base + threadIdx.x;
     int b = -1;
     uint32_t loc = 0;
     if (r < owned) {
       uint64_t deg = off[r + 1] - off[r];
-      b = deg < kSmallDeg ? 0 : (deg < kMidDeg ? 1 : 2);
-      loc = atomicAdd(&s_cnt[b], 1u);
+      if (deg) {
+        b = deg < kSmallDeg ? 0 : (deg < kMidDeg ? 1 : 2);
+        loc = atomicAdd(&s_cnt[b], 1u);
+      } else if (out_off[r + 1] == out_off[r]) {
+        atomicAdd(&s_cnt[r < owned_real ? 3 : 4], 1u);
+      }
     }
     __syncthreads();
-    if (threadIdx.x < 3 && s_cnt[threadIdx.x])
-      s_base[threadIdx.x] =
-          atomicAdd(gcnt[threadIdx.x],
+    if (threadIdx.x < 5 && s_cnt[threadIdx.x]) {
+      unsigned long long at =
+          atomicAdd(cnt + threadIdx.x,
                     static_cast<unsigned long long>(s_cnt[threadIdx.x]));
+      if (threadIdx.x < 3) s_base[threadIdx.x] = at;
+    }
     __syncthreads();
     if (b >= 0) lists[b][s_base[b] + loc] = r;
     __syncthreads();
   }
+}
+
+// One bitmap word per thread: bit r%32 of word r/32 is set when owned row r
+// has an edge. No atomics; compacted into rows_active (ascending).
+__global__ void active_rows_bitmap_kernel(
+    const uint64_t* __restrict__ off, const uint64_t* __restrict__ out_off,
+    uint32_t owned, uint32_t* __restrict__ words, size_t nwords) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t w = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+       w < nwords; w += stride) {
+    uint32_t bits = 0;
+    for (int b = 0; b < 32; ++b) {
+      uint64_t r = (static_cast<uint64_t>(w) << 5) + b;
+      if (r < owned && row_has_edges(off, out_off, static_cast<uint32_t>(r)))
+        bits |= 1u << b;
+    }
+    words[w] = bits;
+  }
+}
+
+// degrees of a row list (hub work-list build)
+__global__ void gather_row_deg_kernel(const uint64_t* __restrict__ off,
+                                      const uint32_t* __restrict__ rows,
+                                      uint64_t nrows,
+                                      uint64_t* __restrict__ deg) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < nrows; i += stride)
+    deg[i] = off[rows[i] + 1] - off[rows[i]];
+}
+
+// PageRank epilogue of the fused path: every owned row outside rows_active
+// (isolated, padding included as before) takes the last iteration's base.
+// Tests the degree offsets instead of keeping a list of the isolated rows
+// (296M entries at the benchmark shape).
+__global__ void pr_fill_isolated_kernel(
+    const uint64_t* __restrict__ off, const uint64_t* __restrict__ out_off,
+    uint32_t owned, uint32_t v_begin, const double* __restrict__ last_base,
+    double* __restrict__ rank) {
+  const double base = *last_base;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       r < owned; r += stride)
+    if (!row_has_edges(off, out_off, static_cast<uint32_t>(r)))
+      rank[v_begin + r] = base;
 }
 
 // Phase-split pulls (multi-GPU compute/comm overlap): the per-row
@@ -1518,21 +1599,32 @@ __global__ void pr_pull_mid_kernel(const uint64_t* __restrict__ off,
   }
 }
 
-// block per row
+// Hub rows (>= kMidDeg arcs): block per (row, segment) item of kHubSeg
+// arcs, so a 0.7M-arc row spreads over ~170 blocks instead of serialising
+// one. Each item writes one fp64 partial; pr_hub_reduce_kernel folds a
+// row's partials in a fixed order (no fp64 atomics: results stay
+// run-to-run deterministic). Segments are cut over the PHASE's span, so
+// items past its end write 0.
+constexpr uint32_t kHubSeg = 4096;
+
 template <int PHASE>
 __global__ void pr_pull_large_kernel(const uint64_t* __restrict__ off,
                                      const uint32_t* __restrict__ dst,
                                      const float* __restrict__ contrib,
                                      const uint32_t* __restrict__ rows,
-                                     uint64_t nrows, uint32_t v_begin,
-                                     uint32_t lo, uint32_t hi,
-                                     double* __restrict__ acc) {
+                                     const uint32_t* __restrict__ item_row,
+                                     const uint32_t* __restrict__ item_seg,
+                                     uint64_t nitems, uint32_t lo,
+                                     uint32_t hi,
+                                     double* __restrict__ part) {
   __shared__ double s_wave[kBlock / kWave];
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
-    uint32_t r = rows[i];
+  for (uint64_t i = blockIdx.x; i < nitems; i += gridDim.x) {
+    uint32_t r = rows[item_row[i]];
     PrSpan sp = pr_span<PHASE>(dst, off[r], off[r + 1], lo, hi);
+    uint64_t kb = static_cast<uint64_t>(item_seg[i]) * kHubSeg;
+    uint64_t ke = kb + kHubSeg < sp.n() ? kb + kHubSeg : sp.n();
     double sum = 0;
-    for (uint64_t k = threadIdx.x; k < sp.n(); k += blockDim.x)
+    for (uint64_t k = kb + threadIdx.x; k < ke; k += blockDim.x)
       sum += contrib[dst[sp.map(k)]];
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
@@ -1542,10 +1634,37 @@ __global__ void pr_pull_large_kernel(const uint64_t* __restrict__ off,
       double t = 0;
 #pragma unroll
       for (int w = 0; w < kBlock / kWave; ++w) t += s_wave[w];
-      if (PHASE == 2) acc[v_begin + r] += t;
-      else acc[v_begin + r] = t;
+      part[i] = t;
     }
     __syncthreads();
+  }
+}
+
+// wave per hub row: lanes stride the row's partials, then a fixed shuffle
+// tree; the same order on every run.
+template <int PHASE>
+__global__ void pr_hub_reduce_kernel(const uint32_t* __restrict__ rows,
+                                     const uint32_t* __restrict__ row_first,
+                                     uint64_t nrows,
+                                     const double* __restrict__ part,
+                                     uint32_t v_begin,
+                                     double* __restrict__ acc) {
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int waves_per_block = kBlock / kWave;
+  size_t wstride = static_cast<size_t>(gridDim.x) * waves_per_block;
+  for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * waves_per_block + wid;
+       j < nrows; j += wstride) {
+    double sum = 0;
+    for (uint32_t k = row_first[j] + lane; k < row_first[j + 1]; k += kWave)
+      sum += part[k];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) sum += __shfl_down(sum, d, 64);
+    if (lane == 0) {
+      uint32_t r = rows[j];
+      if (PHASE == 2) acc[v_begin + r] += sum;
+      else acc[v_begin + r] = sum;
+    }
   }
 }
 
@@ -2481,23 +2600,94 @@ namespace grapehip {
 // Degree buckets over the pull CSR (undirected: out == neighborhood;
 // directed: in-CSR). Built once per graph, reused by PR pull + BFS pull.
 // ---------------------------------------------------------------------------
-static void ensure_buckets(DeviceGraph& g, hipStream_t s) {
+static uint64_t compact_frontier(GpuContext::Impl& I, uint32_t* bm_words,
+                                 size_t nbits, uint32_t bit_base, uint32_t* q,
+                                 hipStream_t s);
+
+// Also builds rows_active and the hub work list (see DeviceGraph). All of
+// it hangs off the DeviceGraph and is built once: a mutated graph is
+// re-uploaded as a fresh DeviceGraph, and the cached PageRank hipGraph that
+// bakes these pointers is destroyed before the buffers in ~DeviceGraph.
+static void ensure_buckets(DeviceGraph& g, GpuContext::Impl& I,
+                           hipStream_t s) {
   if (g.buckets_built) return;
   uint32_t owned = g.owned();
   const uint64_t* pull_off = !g.directed ? g.oe_off.data() : g.ie_off.data();
+  const uint64_t* out_off = g.oe_off.data();
   g.rows_small.resize(owned);
   g.rows_mid.resize(owned);
   g.rows_large.resize(owned);
-  DeviceBuffer<unsigned long long> cnts(3);
+  DeviceBuffer<unsigned long long> cnts(5);
   cnts.zero(s);
   bucket_rows_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-      pull_off, owned, g.rows_small.data(), cnts.data() + 0,
-      g.rows_mid.data(), cnts.data() + 1, g.rows_large.data(),
-      cnts.data() + 2);
+      pull_off, out_off, owned, g.owned_real, g.rows_small.data(),
+      g.rows_mid.data(), g.rows_large.data(), cnts.data());
   auto h = cnts.download(s);
   g.n_small = h[0];
   g.n_mid = h[1];
   g.n_large = h[2];
+  g.n_isolated_real = h[3];
+  g.n_isolated_pad = h[4];
+
+  // rows_active: bitmap of rows with an edge, compacted in ascending order
+  g.n_active = owned - g.n_isolated_real - g.n_isolated_pad;
+  g.rows_active.resize(g.n_active ? g.n_active : 1);
+  if (g.n_active) {
+    size_t nwords = (static_cast<size_t>(owned) + 31) / 32;
+    DeviceBuffer<uint32_t> bm(nwords);
+    active_rows_bitmap_kernel<<<grid_for(nwords), kBlock, 0, s>>>(
+        pull_off, out_off, owned, bm.data(), nwords);
+    uint64_t got =
+        compact_frontier(I, bm.data(), owned, 0, g.rows_active.data(), s);
+    HIP_CHECK(hipStreamSynchronize(s));  // bm is freed on return
+    if (got != g.n_active)
+      throw std::runtime_error("buckets: active-row count mismatch");
+  }
+
+  // hub work list, built on the host: n_large <= E / kMidDeg rows
+  g.n_hub_items = 0;
+  if (g.n_large) {
+    std::vector<uint32_t> rows(g.n_large);
+    HIP_CHECK(hipMemcpyAsync(rows.data(), g.rows_large.data(),
+                             g.n_large * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    // the block-aggregated reservation leaves the list in no fixed order;
+    // sort it so the item order (and with it every hub sum) is the same
+    // for every build of the same graph
+    std::sort(rows.begin(), rows.end());
+    HIP_CHECK(hipMemcpyAsync(g.rows_large.data(), rows.data(),
+                             g.n_large * 4, hipMemcpyHostToDevice, s));
+    DeviceBuffer<uint64_t> d_deg(g.n_large);
+    gather_row_deg_kernel<<<grid_for(g.n_large), kBlock, 0, s>>>(
+        pull_off, g.rows_large.data(), g.n_large, d_deg.data());
+    auto deg = d_deg.download(s);
+    std::vector<uint32_t> item_row, item_seg, row_first(g.n_large + 1);
+    for (uint64_t j = 0; j < g.n_large; ++j) {
+      row_first[j] = static_cast<uint32_t>(item_row.size());
+      uint64_t nseg = (deg[j] + kHubSeg - 1) / kHubSeg;
+      if (item_row.size() + nseg > 0xFFFFFFFFull)
+        throw std::runtime_error("buckets: hub work list too large");
+      for (uint64_t k = 0; k < nseg; ++k) {
+        item_row.push_back(static_cast<uint32_t>(j));
+        item_seg.push_back(static_cast<uint32_t>(k));
+      }
+    }
+    row_first[g.n_large] = static_cast<uint32_t>(item_row.size());
+    g.n_hub_items = item_row.size();
+    g.hub_item_row.upload(item_row, s);
+    g.hub_item_seg.upload(item_seg, s);
+    g.hub_row_first.upload(row_first, s);
+    g.pr_hub_part.resize(g.n_hub_items);
+    HIP_CHECK(hipStreamSynchronize(s));  // host vectors go out of scope
+  }
+  if (getenv("GRAPEHIP_DEBUG"))
+    fprintf(stderr,
+            "[buckets] owned=%u small=%lu mid=%lu large=%lu active=%lu "
+            "isolated=%lu isolated_pad=%lu hub_items=%lu\n",
+            owned, (unsigned long)g.n_small, (unsigned long)g.n_mid,
+            (unsigned long)g.n_large, (unsigned long)g.n_active,
+            (unsigned long)g.n_isolated_real,
+            (unsigned long)g.n_isolated_pad, (unsigned long)g.n_hub_items);
   g.buckets_built = true;
 }
 
@@ -3016,7 +3206,7 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
   bool multi = world_ > 1;
 
   const bool pull_capable = !g.directed || g.has_in;
-  if (pull_capable) ensure_buckets(g, s);
+  if (pull_capable) ensure_buckets(g, I, s);
   if (multi && pull_capable) ensure_mirrors(I, comm_, g, rank_, world_, s);
   const uint64_t* pull_off = !g.directed ? g.oe_off.data() : g.ie_off.data();
   const uint32_t* pull_dst = !g.directed ? g.oe_dst.data() : g.ie_dst.data();
@@ -3345,7 +3535,7 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
       (!g.directed ? g.oe_off.data() : g.ie_off.data());
   const uint32_t* pull_dst =
       (!g.directed ? g.oe_dst.data() : g.ie_dst.data());
-  if (pull) ensure_buckets(g, s);
+  if (pull) ensure_buckets(g, I, s);
   if (pull && multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
   // dst-tiled pull stream: auto-selected by density. On sparse shapes
   // (datagen mean degree ~5) the short per-src runs mean one fp64 L2
@@ -3368,13 +3558,14 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
     g.pr_rank.resize(nv_pad);
     g.pr_acc.resize(nv_pad);
     g.pr_contrib.resize(nv_pad);
-    g.pr_dangling.resize(1);
+    g.pr_dangling.resize(3);
   }
   DeviceBuffer<double>& rank_arr = g.pr_rank;
   DeviceBuffer<double>& acc = g.pr_acc;
   DeviceBuffer<float>& contrib = g.pr_contrib;
   DeviceBuffer<double>& d_dangling = g.pr_dangling;
-  if (d_dangling.size() < 2) d_dangling.resize(2);  // [0]=cur, [1]=next
+  // [0]=cur, [1]=next, [2]=previous base (isolated rows' closed form)
+  if (d_dangling.size() < 3) d_dangling.resize(3);
   DeviceBuffer<double> d_l1(tol > 0 ? 1 : 0);
   DevGraphView view = make_view(g, rank_, world_);
 
@@ -3384,6 +3575,11 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
   const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
 
   fill(rank_arr.data(), 1.0 / N, nv_pad, s);
+  // Rows without a pull edge are in no bucket, so the row pulls never write
+  // their acc, yet it is read for rows that have out-edges only (directed)
+  // and by the multi-GPU apply over all owned rows. The buffer is shared
+  // with the tiled and push paths; clear it once per call.
+  if (pull && !tiled) acc.zero(s);
   int rounds = 0;
   const double inv_n = 1.0 / N;
 
@@ -3399,11 +3595,17 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
         pr_pull_mid_kernel<P><<<grid_for(g.n_mid * kWave), kBlock, 0, s>>>(
             pull_off, pull_dst, contrib.data(), g.rows_mid.data(), g.n_mid,
             g.v_begin, g.v_begin, g.v_end, acc.data());
-      if (g.n_large)
-        pr_pull_large_kernel<P><<<std::min<uint64_t>(g.n_large, kMaxGrid),
+      if (g.n_large) {
+        pr_pull_large_kernel<P><<<std::min<uint64_t>(g.n_hub_items, kMaxGrid),
                                   kBlock, 0, s>>>(
             pull_off, pull_dst, contrib.data(), g.rows_large.data(),
-            g.n_large, g.v_begin, g.v_begin, g.v_end, acc.data());
+            g.hub_item_row.data(), g.hub_item_seg.data(), g.n_hub_items,
+            g.v_begin, g.v_end, g.pr_hub_part.data());
+        pr_hub_reduce_kernel<P><<<grid_for(g.n_large * kWave), kBlock, 0,
+                                  s>>>(
+            g.rows_large.data(), g.hub_row_first.data(), g.n_large,
+            g.pr_hub_part.data(), g.v_begin, acc.data());
+      }
     };
     if (phase == 0) launch(std::integral_constant<int, 0>{});
     else if (phase == 1) launch(std::integral_constant<int, 1>{});
@@ -3431,6 +3633,7 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
   const bool fused = pull && !multi;
   auto fused_bootstrap = [&]() {
     d_dangling.zero(s);
+    fill(d_dangling.data() + 2, inv_n, 1, s);  // isolated rows start at 1/N
     pr_dangling_kernel<<<grid_for(g.owned_real), kBlock, 0, s>>>(
         rank_arr.data(), g.oe_off.data(), g.owned_real, g.v_begin,
         d_dangling.data());
@@ -3453,10 +3656,11 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
     }
     HIP_CHECK(hipMemsetAsync(d_dangling.data() + 1, 0, 8, s));
     if (tol > 0) d_l1.zero(s);
-    pr_fused_apply_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+    pr_fused_apply_kernel<<<grid_for(g.n_active), kBlock, 0, s>>>(
         rank_arr.data(), acc.data(), d_dangling.data(), inv_n, damping,
-        g.v_begin, owned, g.owned_real, g.oe_off.data(),
-        contrib.data() + g.v_begin, d_dangling.data() + 1,
+        g.v_begin, g.rows_active.data(), g.n_active, g.owned_real,
+        static_cast<double>(g.n_isolated_real), d_dangling.data() + 2,
+        g.oe_off.data(), contrib.data() + g.v_begin, d_dangling.data() + 1,
         tol > 0 ? d_l1.data() : nullptr);
     HIP_CHECK(hipMemcpyAsync(d_dangling.data(), d_dangling.data() + 1, 8,
                              hipMemcpyDeviceToDevice, s));
@@ -3586,6 +3790,12 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
       if (l1 < tol) break;
     }
   }
+  // the fused iterations left the isolated rows to the scalar recurrence;
+  // complete the device-resident result (outside the captured graph)
+  if (fused)
+    pr_fill_isolated_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+        pull_off, g.oe_off.data(), owned, g.v_begin, d_dangling.data() + 2,
+        rank_arr.data());
   HIP_CHECK(hipDeviceSynchronize());
   if (comm_) comm_->barrier();
   double t1 = wall_s();

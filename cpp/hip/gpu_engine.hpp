@@ -37,8 +37,26 @@ struct DeviceGraph {
   DeviceBuffer<float> ie_w;
   // degree buckets over owned rows (built lazily; row-per-thread/wave/block
   // scheduling for whole-graph sweeps — the CTA scheduler, preprocessed)
+  // Rows with no pull edge are in no bucket: a PageRank pull sums nothing
+  // for them and a BFS pull can find them no parent.
   DeviceBuffer<uint32_t> rows_small, rows_mid, rows_large;
   uint64_t n_small = 0, n_mid = 0, n_large = 0;
+  // rows_active: ascending owned rows with an edge in the pull CSR or the
+  // out-CSR; its complement is the isolated set, whose PageRank follows a
+  // scalar recurrence. Padding rows (>= owned_real) carry no edges
+  // (upload pads their offsets flat), so they are never active and never
+  // counted in n_isolated_real.
+  DeviceBuffer<uint32_t> rows_active;
+  uint64_t n_active = 0, n_isolated_real = 0, n_isolated_pad = 0;
+  // hub work list: every rows_large row cut into kHubSeg-arc items, in row
+  // order. hub_item_row[i] indexes rows_large, hub_item_seg[i] is the
+  // segment within the row, hub_row_first[j] the first item of row j
+  // (n_large + 1 entries). pr_hub_part holds one fp64 partial per item.
+  // All built with the buckets and alive as long as the graph: the cached
+  // PageRank hipGraph bakes their pointers.
+  DeviceBuffer<uint32_t> hub_item_row, hub_item_seg, hub_row_first;
+  DeviceBuffer<double> pr_hub_part;
+  uint64_t n_hub_items = 0;
   bool buckets_built = false;
   // mirror topology (multi-GPU, built lazily): the reference's mirror-info /
   // BatchShuffle design (edgecut_fragment_base.h:569+, cuda batch_shuffle
@@ -77,6 +95,7 @@ struct DeviceGraph {
   double pr_graph_damping = 0.0;
   int pr_calls = 0;  // capture lazily: one-shot runs skip the ~10ms
                      // instantiate; repeated runs (bench warmup) get it
+  // pr_dangling: [0]=current dangling sum, [1]=next, [2]=previous base
   DeviceBuffer<double> pr_rank, pr_acc, pr_dangling;
   DeviceBuffer<float> pr_contrib;
   ~DeviceGraph();

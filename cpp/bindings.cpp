@@ -827,7 +827,18 @@ PYBIND11_MODULE(_core, m) {
            },
            py::arg("graph"), py::arg("source") = 0)
       .def("kcore",
-           [](PyEngine& eng, PyGraph& g, int k) {
+           [](PyEngine& eng, PyGraph& g, int k, bool values) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (eng.use_gpu && g.dev) {
+               GpuRunResult r;
+               {
+                 py::gil_scoped_release rel;
+                 r = eng.gpu->kcore(*g.dev, k, values);
+               }
+               return gpu_dict(r, g, /*is_i64=*/true, values);
+             }
+#endif
+             (void)values;  // the host path always returns them
              if (!g.frag)
                throw std::runtime_error("kcore needs a host fragment");
              KCoreApp app;
@@ -844,9 +855,20 @@ PYBIND11_MODULE(_core, m) {
              meta["values"] = to_np(vals);
              return meta;
            },
-           py::arg("graph"), py::arg("k") = 3)
+           py::arg("graph"), py::arg("k") = 3, py::arg("values") = true)
       .def("core_decomposition",
-           [](PyEngine& eng, PyGraph& g) {
+           [](PyEngine& eng, PyGraph& g, bool values) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (eng.use_gpu && g.dev) {
+               GpuRunResult r;
+               {
+                 py::gil_scoped_release rel;
+                 r = eng.gpu->core_decomposition(*g.dev, values);
+               }
+               return gpu_dict(r, g, /*is_i64=*/true, values);
+             }
+#endif
+             (void)values;  // the host path always returns them
              if (!g.frag)
                throw std::runtime_error(
                    "core_decomposition needs a host fragment");
@@ -864,7 +886,7 @@ PYBIND11_MODULE(_core, m) {
              meta["values"] = to_np(vals);
              return meta;
            },
-           py::arg("graph"))
+           py::arg("graph"), py::arg("values") = true)
       .def("load_vertexcut",
            [](PyEngine& eng, arr_i64 src, arr_i64 dst, int64_t num_vertices,
               int bucket_num) {

@@ -10,6 +10,8 @@
 //     bitmap + per-peer regions) exchanged with paired ncclSend/Recv over
 //     xGMI, lengths via the TCP control plane
 //   * cuda apps bfs/sssp/pagerank/wcc -> drivers below
+//   * examples/analytical_apps/kcore/kcore.h and core_decomposition/
+//     core_decomposition.h (CPU only in the reference) -> frontier peeling
 #include "gpu_engine.hpp"
 
 #include <rccl/rccl.h>
@@ -17,7 +19,9 @@
 #include <algorithm>
 #include <cmath>
 #include <functional>
+#include <climits>
 #include <cstring>
+#include <type_traits>
 #include <unordered_map>
 
 #include "dev_graph.hpp"
@@ -755,7 +759,11 @@ __global__ void expand_wm_frontier(DevGraphView g,
     uint64_t incl = wave_incl_scan(deg);
     uint64_t total = __shfl(static_cast<unsigned long long>(incl), 63, 64);
     uint64_t excl = incl - deg;
-    for (uint64_t e = lane; e < total; e += kWave) {
+    // whole-wave trips: the probes below read other lanes' registers, and
+    // a lane that had left the loop (last trip of a chunk whose edge count
+    // is no multiple of 64) holds no defined answer
+    for (uint64_t e0 = 0; e0 < total; e0 += kWave) {
+      const uint64_t e = e0 + lane;
       int lo = 0, hi = 63;
 #pragma unroll
       for (int step = 0; step < 6; ++step) {
@@ -768,8 +776,10 @@ __global__ void expand_wm_frontier(DevGraphView g,
       uint32_t uo = __shfl(u, lo, 64);
       uint64_t bo = __shfl(static_cast<unsigned long long>(b), lo, 64);
       uint64_t po = __shfl(static_cast<unsigned long long>(excl), lo, 64);
-      uint64_t eid = bo + (e - po);
-      op(uo, g.oe_dst[eid], g.oe_w ? g.oe_w[eid] : 1.0f);
+      if (e < total) {
+        uint64_t eid = bo + (e - po);
+        op(uo, g.oe_dst[eid], g.oe_w ? g.oe_w[eid] : 1.0f);
+      }
     }
   }
 }
@@ -844,6 +854,27 @@ __global__ void halo_pack_kernel(const uint32_t* __restrict__ idx, uint64_t n,
     uint32_t v = idx[i];
     out[i].v = v;
     out[i].val = state[v];
+    bm.clear_bit(v);
+  }
+}
+
+// Take-and-zero pack for accumulated state (k-core decrement counts): ships
+// (v, state[v]) and leaves state[v] == 0 for the next flush. No adder runs
+// concurrently (the expansion kernel precedes it on the stream), so a plain
+// read + store suffices.
+template <typename T>
+__global__ void halo_pack_take_kernel(const uint32_t* __restrict__ idx,
+                                      uint64_t n, T* __restrict__ state,
+                                      DevBitmap bm,
+                                      HaloPair<T>* __restrict__ out) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < n; i += stride) {
+    uint32_t v = idx[i];
+    out[i].v = v;
+    out[i].val = state[v];
+    state[v] = T(0);
     bm.clear_bit(v);
   }
 }
@@ -1301,6 +1332,136 @@ __global__ void wcc_mark_rest_kernel(const uint32_t* __restrict__ parent,
     if (parent[v_begin + r] != giant && off[r + 1] != off[r])
       bm.set_once(r);
 }
+
+// ===========================================================================
+// k-core / core decomposition by level-synchronous frontier peeling.
+// Reference parity: examples/analytical_apps/kcore/kcore.h and
+// core_decomposition/core_decomposition.h (the reference runs both on the
+// CPU only). Semantics are cpp/apps/kcore.hpp's: residual degree = stored
+// out-CSR row length with multiplicity, self-loops excluded; peeling a
+// vertex decrements each stored out-neighbour once per arc.
+// deg/core are indexed by owned row; deg is signed so a peeled vertex may
+// keep falling below its level. core[r] < 0 means "not peeled yet".
+// ===========================================================================
+
+// deg[r] = row length. Rows of 2^31 arcs or more raise *too_long (the host
+// throws); the owner-searched self-loop sweep below does the correction, so
+// no thread walks a row here.
+__global__ void kcore_init_deg_kernel(const uint64_t* __restrict__ off,
+                                      uint32_t owned, int* __restrict__ deg,
+                                      int* __restrict__ too_long) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < owned;
+       r += stride) {
+    uint64_t len = off[r + 1] - off[r];
+    if (len > static_cast<uint64_t>(INT_MAX)) *too_long = 1;
+    deg[r] = static_cast<int>(len);
+  }
+}
+
+// expand_cm_range op: one decrement per stored self-loop arc
+struct KcoreSelfLoopOp {
+  int* deg;
+  uint32_t v_begin;
+  __device__ __forceinline__ void operator()(uint32_t u, uint32_t d,
+                                             float) const {
+    if (d == u) atomicSub(&deg[u - v_begin], 1);
+  }
+};
+
+// min residual degree over the rows not yet peeled (INT_MAX if none):
+// wave64 shuffle, LDS across the block's waves, one atomicMin per block
+__global__ void kcore_min_alive_kernel(const int* __restrict__ deg,
+                                       const int* __restrict__ core,
+                                       uint32_t rows, int* __restrict__ out) {
+  __shared__ int s_wave[kBlock / kWave];
+  int m = INT_MAX;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < rows;
+       r += stride)
+    if (core[r] < 0) m = min(m, deg[r]);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) m = min(m, __shfl_down(m, d, 64));
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = INT_MAX;
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; ++w) t = min(t, s_wave[w]);
+    if (t != INT_MAX) atomicMin(out, t);
+  }
+}
+
+// Seed the (all-zero) owned-row bitmap with the unpeeled rows at or below
+// the level. One lane per row; a wave ballots its 64 rows into two whole
+// bitmap words, so no atomics. Every lane of a wave runs the same trips
+// (the stride is a multiple of 64 and the bound is on the wave's base row).
+__global__ void kcore_seed_kernel(const int* __restrict__ deg,
+                                  const int* __restrict__ core,
+                                  uint32_t rows, int level,
+                                  uint32_t* __restrict__ bm_words) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                       (threadIdx.x - lane);
+       base < rows; base += stride) {
+    uint64_t r = base + lane;
+    bool hit = r < rows && core[r] < 0 && deg[r] <= level;
+    unsigned long long mask = __ballot(hit);
+    if (lane == 0)
+      bm_words[base >> 5] = static_cast<uint32_t>(mask);
+    else if (lane == 32 && r < rows)
+      bm_words[r >> 5] = static_cast<uint32_t>(mask >> 32);
+  }
+}
+
+// record the level of every queued vertex (seeds and crossers alike)
+__global__ void kcore_stamp_kernel(const uint32_t* __restrict__ q,
+                                   uint32_t qn, uint32_t v_begin, int level,
+                                   int* __restrict__ core) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < qn;
+       i += stride)
+    core[q[i] - v_begin] = level;
+}
+
+// Peel arc u->d. The crossing test (old above the level, new at or below
+// it) fires for exactly one decrement per vertex, so each vertex enters a
+// frontier once with no separate alive check: vertices already peeled or
+// already queued sit at or below the level and can never cross again.
+struct KcoreOp {
+  int* deg;
+  int level;
+  DevBitmap next_bm;  // over owned bits
+  uint32_t v_begin, v_end;
+  bool multi;
+  uint32_t* dec;  // multi-rank: pending decrements per remote vertex
+  DevHalo halo;
+  __device__ __forceinline__ void operator()(uint32_t u, uint32_t d,
+                                             float) const {
+    if (d == u) return;
+    if (d >= v_begin && d < v_end) {
+      int old = atomicSub(&deg[d - v_begin], 1);
+      if (old > level && old - 1 <= level) next_bm.set_once(d - v_begin);
+    } else if (multi) {
+      atomicAdd(&dec[d], 1u);
+      halo.add(d);
+    }
+  }
+};
+
+struct KcoreRecvOp {  // incoming (v, count) — v owned here
+  int* deg;
+  int level;
+  DevBitmap next_bm;
+  uint32_t v_begin;
+  __device__ __forceinline__ void operator()(uint32_t v, uint32_t c) const {
+    // c counts arcs into v, fewer than 2^31 (the driver checks)
+    int ci = static_cast<int>(c);
+    int old = atomicSub(&deg[v - v_begin], ci);
+    if (old > level && old - ci <= level) next_bm.set_once(v - v_begin);
+  }
+};
 
 }  // namespace grapehip
 
@@ -2780,10 +2941,13 @@ static uint64_t compact_frontier(GpuContext::Impl& I, uint32_t* bm_words,
 // ---------------------------------------------------------------------------
 // Halo host-side flush: pack per-peer pairs, exchange counts over TCP,
 // ncclSend/Recv payloads over xGMI. Returns #received pairs (in recvbuf).
+// TAKE packs with halo_pack_take_kernel: the packed state entries are zero
+// again afterwards (accumulators such as the k-core decrement counts).
 // ---------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool TAKE = false>
 uint64_t halo_flush(GpuContext::Impl& I, TcpComm* comm, int rank, int world,
-                    const T* state, uint64_t cap, hipStream_t s) {
+                    std::conditional_t<TAKE, T*, const T*> state,
+                    uint64_t cap, hipStream_t s) {
   std::vector<unsigned long long> cnts(world);
   HIP_CHECK(hipMemcpyAsync(cnts.data(), I.halo_cnt.data(), world * 8,
                            hipMemcpyDeviceToHost, s));
@@ -2801,10 +2965,14 @@ uint64_t halo_flush(GpuContext::Impl& I, TcpComm* comm, int rank, int world,
     send_off[p + 1] = send_off[p] + cnts[p] * pair_sz;
   for (int p = 0; p < world; ++p) {
     if (!cnts[p]) continue;
-    halo_pack_kernel<T><<<grid_for(cnts[p]), kBlock, 0, s>>>(
-        I.halo_idx.data() + static_cast<uint64_t>(p) * cap, cnts[p], state,
-        DevBitmap{I.halo_bm.data()},
-        reinterpret_cast<HaloPair<T>*>(I.sendbuf.data() + send_off[p]));
+    const uint32_t* idx = I.halo_idx.data() + static_cast<uint64_t>(p) * cap;
+    auto* out = reinterpret_cast<HaloPair<T>*>(I.sendbuf.data() + send_off[p]);
+    if constexpr (TAKE)
+      halo_pack_take_kernel<T><<<grid_for(cnts[p]), kBlock, 0, s>>>(
+          idx, cnts[p], state, DevBitmap{I.halo_bm.data()}, out);
+    else
+      halo_pack_kernel<T><<<grid_for(cnts[p]), kBlock, 0, s>>>(
+          idx, cnts[p], state, DevBitmap{I.halo_bm.data()}, out);
   }
   I.halo_cnt.zero(s);
   // exchange the count matrix on the control plane
@@ -6713,6 +6881,182 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
     HIP_CHECK(hipStreamSynchronize(s));
   }
   return res;
+}
+
+}  // namespace grapehip
+
+namespace grapehip {
+
+// ---------------------------------------------------------------------------
+// k-core / core decomposition (frontier peeling; kernels in the app-functor
+// section above). Reference parity: examples/analytical_apps/kcore/kcore.h
+// and core_decomposition/core_decomposition.h.
+//
+// Level k is the minimum residual degree over the unpeeled owned rows (min
+// across ranks), so empty levels are jumped. Within a level, sub-rounds
+// expand the frontier through expand_frontier (GRAPEHIP_LB applies) until no
+// rank has a vertex left at or below k. kcore(k) is the single level k - 1.
+// Multi-rank: decrements of remote vertices accumulate in dec[] (global
+// size, zero between flushes) and travel as (v, count) halo pairs; frontier
+// emptiness and the level are agreed on the TCP control plane.
+// Only real rows (< owned_real) are seeded or reduced over: padding rows
+// have no arcs, are never referenced, and are cut from the results.
+// ---------------------------------------------------------------------------
+GpuRunResult GpuContext::peel(DeviceGraph& g, bool all_levels, int k,
+                              bool fetch) {
+  auto& I = *impl_;
+  hipStream_t s = I.compute;
+  DevGraphView view = make_view(g, rank_, world_);
+  uint32_t nv_pad = padded_nv(g, world_);
+  uint32_t owned = g.owned();
+  uint32_t rows = g.owned_real;
+  uint64_t cap = view.slice;
+  bool multi = world_ > 1;
+  // a directed vertex can lose up to its in-degree below zero; in-degrees
+  // are not stored, so bound them by the arc total
+  if (g.directed && g.total_edges > static_cast<uint64_t>(INT_MAX))
+    throw std::runtime_error(
+        "kcore: directed graphs need fewer than 2^31 arcs on the device");
+
+  DeviceBuffer<int> deg(owned ? owned : 1);
+  DeviceBuffer<int> core(owned ? owned : 1);
+  DeviceBuffer<int> scal(2);  // [0] min alive degree, [1] row-too-long flag
+  DeviceBuffer<uint32_t> q(owned + 64);
+  size_t bm_words = (static_cast<size_t>(owned) + 31) / 32 + 1;
+  DeviceBuffer<uint32_t> next_bm(bm_words);
+  DeviceBuffer<uint32_t> dec(multi ? nv_pad : 1);
+  if (multi) {
+    I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
+    I.halo_cnt.resize(world_);
+    I.halo_bm.resize((static_cast<uint64_t>(nv_pad) + 31) / 32);
+  }
+
+  if (comm_) comm_->barrier();
+  HIP_CHECK(hipDeviceSynchronize());
+  double t0 = wall_s();
+  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+
+  int rounds = 0;
+  core.fill_bytes(0xFF, s);  // -1: not peeled
+  // k <= 0 keeps every vertex: nothing to peel
+  const bool run = all_levels || k > 0;
+  if (run) {
+    next_bm.zero(s);
+    scal.zero(s);
+    if (multi) {
+      dec.zero(s);
+      I.halo_cnt.zero(s);
+      I.halo_bm.zero(s);
+    }
+    kcore_init_deg_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+        g.oe_off.data(), owned, deg.data(), scal.data() + 1);
+    if (owned) {
+      int nchunks = static_cast<int>((owned + kBlock - 1) / kBlock);
+      expand_cm_range<false, KcoreSelfLoopOp>
+          <<<std::min(nchunks, kMaxGrid), kBlock, 0, s>>>(
+              view, KcoreSelfLoopOp{deg.data(), g.v_begin});
+    }
+    int too_long = 0;
+    HIP_CHECK(hipMemcpyAsync(&too_long, scal.data() + 1, 4,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    // agreed across ranks so that nobody is left waiting in a collective
+    if (multi) too_long = comm_->allreduce_or(too_long != 0) ? 1 : 0;
+    if (too_long)
+      throw std::runtime_error("kcore: a row has 2^31 arcs or more");
+  }
+
+  int level = run && !all_levels ? k - 1 : 0;
+  while (run) {
+    if (all_levels) {
+      fill(scal.data(), INT_MAX, 1, s);
+      kcore_min_alive_kernel<<<grid_for(rows), kBlock, 0, s>>>(
+          deg.data(), core.data(), rows, scal.data());
+      int lmin = INT_MAX;
+      HIP_CHECK(hipMemcpyAsync(&lmin, scal.data(), 4, hipMemcpyDeviceToHost,
+                               s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      if (multi) {
+        std::vector<int> all(world_);
+        comm_->allgather(&lmin, sizeof(int), all.data());
+        lmin = *std::min_element(all.begin(), all.end());
+      }
+      if (lmin == INT_MAX) break;  // every vertex on every rank is peeled
+      level = lmin;
+    }
+    kcore_seed_kernel<<<grid_for(rows), kBlock, 0, s>>>(
+        deg.data(), core.data(), rows, level, next_bm.data());
+    uint32_t qn = static_cast<uint32_t>(
+        compact_frontier(I, next_bm.data(), owned, g.v_begin, q.data(), s));
+    uint64_t global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+    int level_rounds = 0;
+    while (global_curr > 0) {
+      if (qn) {
+        kcore_stamp_kernel<<<grid_for(qn), kBlock, 0, s>>>(
+            q.data(), qn, g.v_begin, level, core.data());
+        expand_frontier(
+            I, view, q.data(), qn,
+            KcoreOp{deg.data(), level, DevBitmap{next_bm.data()}, g.v_begin,
+                    g.v_end, multi, dec.data(),
+                    DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
+                            DevBitmap{I.halo_bm.data()}, cap, view.slice,
+                            world_}},
+            s);
+      }
+      if (multi) {
+        uint64_t nrecv = halo_flush<uint32_t, true>(I, comm_, rank_, world_,
+                                                    dec.data(), cap, s);
+        if (nrecv)
+          halo_process_kernel<uint32_t, KcoreRecvOp>
+              <<<grid_for(nrecv), kBlock, 0, s>>>(
+                  reinterpret_cast<HaloPair<uint32_t>*>(I.recvbuf.data()),
+                  nrecv,
+                  KcoreRecvOp{deg.data(), level, DevBitmap{next_bm.data()},
+                              g.v_begin});
+      }
+      qn = static_cast<uint32_t>(
+          compact_frontier(I, next_bm.data(), owned, g.v_begin, q.data(), s));
+      global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+      ++level_rounds;
+    }
+    rounds += level_rounds;
+    if (getenv("GRAPEHIP_DEBUG"))
+      fprintf(stderr, "[kcore] level=%d subrounds=%d t=%.1fms\n", level,
+              level_rounds, (wall_s() - t0) * 1e3);
+    if (!all_levels) break;
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  if (comm_) comm_->barrier();
+  double t1 = wall_s();
+
+  GpuRunResult res;
+  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
+  res.bytes_coll = I.dc.bytes_coll - b_coll0;
+  res.rounds = rounds;
+  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
+  res.traversed_edges = g.input_edges;
+  if (fetch) {
+    std::vector<int> c32(owned);
+    if (owned)
+      HIP_CHECK(hipMemcpyAsync(c32.data(), core.data(), owned * 4ull,
+                               hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    res.i64.resize(owned);
+    for (uint32_t i = 0; i < owned; ++i)
+      res.i64[i] = all_levels ? (c32[i] < 0 ? 0 : c32[i])
+                              : (i < rows && c32[i] < 0 ? 1 : 0);
+  }
+  return res;
+}
+
+GpuRunResult GpuContext::kcore(DeviceGraph& g, int k, bool fetch) {
+  RangeMarker _mk("grapehip::kcore");
+  return peel(g, /*all_levels=*/false, k, fetch);
+}
+
+GpuRunResult GpuContext::core_decomposition(DeviceGraph& g, bool fetch) {
+  RangeMarker _mk("grapehip::core_decomposition");
+  return peel(g, /*all_levels=*/true, 0, fetch);
 }
 
 }  // namespace grapehip

@@ -139,6 +139,11 @@ class GpuContext {
   GpuRunResult cdlp(DeviceGraph& g, int iters, bool fetch = true);
   GpuRunResult lcc(DeviceGraph& g, bool fetch = true);
   GpuRunResult lcc_directed(DeviceGraph& g, bool fetch = true);
+  // frontier peeling on the stored out-CSR (cpp/apps/kcore.hpp semantics)
+  // i64: 1 = in the k-core, 0 = peeled
+  GpuRunResult kcore(DeviceGraph& g, int k, bool fetch = true);
+  // i64: coreness
+  GpuRunResult core_decomposition(DeviceGraph& g, bool fetch = true);
 
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device
@@ -151,6 +156,8 @@ class GpuContext {
   struct Impl;  // internal (kernels + scratch); public for free helpers
 
  private:
+  // shared peeling driver: all levels (coreness) or the single level k - 1
+  GpuRunResult peel(DeviceGraph& g, bool all_levels, int k, bool fetch);
   std::unique_ptr<Impl> impl_;
   TcpComm* comm_;
   int rank_, world_, dev_ = 0;

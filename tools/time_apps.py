@@ -6,8 +6,10 @@ import grapehip
 ap = argparse.ArgumentParser()
 ap.add_argument("--nv", type=int, default=40_000_000)
 ap.add_argument("--ne", type=int, default=101_000_000)
-ap.add_argument("--apps", default="bfs,sssp,pagerank,wcc,cdlp,lcc")
+ap.add_argument("--apps", default="bfs,sssp,pagerank,wcc,cdlp,lcc,kcore,"
+                                  "core_decomposition")
 ap.add_argument("--cdlp-iters", type=int, default=10)
+ap.add_argument("--kcore-k", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1,
                 help="untimed runs per app first (absorbs one-time costs "
                      "like hipGraph capture, matching bench.py)")
@@ -29,6 +31,10 @@ def run_app(app):
         return eng.cdlp(g, args.cdlp_iters, values=False)
     if app == "lcc":
         return eng.lcc(g, values=False)
+    if app == "kcore":
+        return eng.kcore(g, args.kcore_k, values=False)
+    if app == "core_decomposition":
+        return eng.core_decomposition(g, values=False)
     raise SystemExit("unknown app " + app)
 
 
@@ -49,6 +55,8 @@ for app in args.apps.split(","):
         r = eng.cdlp(g, args.cdlp_iters, values=False)
     elif app == "lcc":
         r = eng.lcc(g, values=False)
+    else:
+        r = run_app(app)
     out[app + "_ms"] = round(r["seconds"] * 1e3, 2)
     out[app + "_rounds"] = r["rounds"]
 print(json.dumps(out))

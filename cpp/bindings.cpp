@@ -352,6 +352,23 @@ PYBIND11_MODULE(_core, m) {
              py::gil_scoped_release rel;
              if (e.c()) e.c()->barrier();
            })
+      .def("_debug_expand_counts",
+           [](PyEngine& e, bool reset) {
+#ifdef GRAPEHIP_WITH_HIP
+             auto c = e.gpu->debug_expand_counts(reset);
+             py::dict d;
+             d["cm"] = c[0];
+             d["wm"] = c[1];
+             d["strict"] = c[2];
+             d["none"] = c[3];
+             return d;
+#else
+             (void)reset;
+             throw std::runtime_error("no hip");
+             return py::dict();
+#endif
+           },
+           py::arg("reset") = false)
       .def("_debug_scan",
            [](PyEngine& e, std::vector<uint32_t> in) {
 #ifdef GRAPEHIP_WITH_HIP

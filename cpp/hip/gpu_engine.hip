@@ -2252,6 +2252,8 @@ struct DevComm {
   }
 };
 
+enum LbKind { kLbCm = 0, kLbWm, kLbStrict, kLbNone, kLbCount };
+
 struct GpuContext::Impl {
   DevComm dc;
   Stream compute;
@@ -2274,6 +2276,9 @@ struct GpuContext::Impl {
   DeviceBuffer<uint32_t> frontier_deg;
   DeviceBuffer<uint64_t> frontier_off;
   double t_exchange = 0;
+  // host-side count of frontier-expansion launches per scheduler
+  // (launch_expand only; test hook, see debug_expand_counts)
+  uint64_t expand_counts[kLbCount] = {0, 0, 0, 0};
 };
 
 namespace {
@@ -2370,6 +2375,15 @@ GpuContext::~GpuContext() {
 }
 
 void GpuContext::device_sync() { HIP_CHECK(hipDeviceSynchronize()); }
+
+std::array<uint64_t, 4> GpuContext::debug_expand_counts(bool reset) {
+  std::array<uint64_t, 4> out;
+  for (int i = 0; i < kLbCount; ++i) {
+    out[i] = impl_->expand_counts[i];
+    if (reset) impl_->expand_counts[i] = 0;
+  }
+  return out;
+}
 
 std::vector<uint64_t> GpuContext::debug_scan(const std::vector<uint32_t>& in) {
   hipStream_t s = impl_->compute;
@@ -3327,7 +3341,38 @@ __global__ void wcc_relabel_kernel(const uint32_t* __restrict__ parent,
     out[i] = m[parent[v_begin + i]];
 }
 
-// generic frontier expansion helper: scan degrees then CM-expand
+// Scheduler dispatch (reference --lb flag, default cta/cm) over a frontier
+// whose degree prefix `offsets` (qn + 1 entries, `total` arcs) is already
+// scanned: cm = LDS-staged owner search; wm = wave-granular register-staged
+// CM; strict = perfectly edge-balanced; none = thread-per-row. Every
+// frontier expansion launches from here, and only here is it counted.
+template <typename Op>
+void launch_expand(GpuContext::Impl& I, const DevGraphView& view,
+                   const uint32_t* q, uint32_t qn, const uint64_t* offsets,
+                   uint64_t total, Op op, hipStream_t s) {
+  if (qn == 0) return;
+  static const char* lb = getenv("GRAPEHIP_LB");
+  if (lb && lb[0] == 's') {
+    ++I.expand_counts[kLbStrict];
+    expand_strict_frontier<Op><<<grid_for(total), kBlock, 0, s>>>(
+        view, q, qn, offsets, total, op);
+  } else if (lb && lb[0] == 'n') {
+    ++I.expand_counts[kLbNone];
+    expand_none_frontier<Op><<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
+                                                             op);
+  } else if (lb && lb[0] == 'w') {
+    ++I.expand_counts[kLbWm];
+    expand_wm_frontier<Op><<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
+                                                           op);
+  } else {
+    ++I.expand_counts[kLbCm];
+    int nchunks = static_cast<int>((qn + kBlock - 1) / kBlock);
+    expand_cm_frontier<Op><<<std::min(nchunks, kMaxGrid), kBlock, 0, s>>>(
+        view, q, qn, offsets, op);
+  }
+}
+
+// generic frontier expansion helper: scan degrees, then launch_expand
 template <typename Op>
 void expand_frontier(GpuContext::Impl& I, const DevGraphView& view,
                      const uint32_t* q, uint32_t qn, Op op, hipStream_t s) {
@@ -3339,24 +3384,7 @@ void expand_frontier(GpuContext::Impl& I, const DevGraphView& view,
                                                     I.frontier_deg.data());
   uint64_t total = exclusive_scan(I.frontier_deg.data(),
                                   I.frontier_off.data(), qn, s, I.scan);
-  // LB strategy (reference --lb flag, default cta/cm): cm = LDS-staged
-  // owner search; wm = wave-granular register-staged CM; strict =
-  // perfectly edge-balanced; none = thread-per-row
-  static const char* lb = getenv("GRAPEHIP_LB");
-  if (lb && lb[0] == 's') {
-    expand_strict_frontier<Op><<<grid_for(total), kBlock, 0, s>>>(
-        view, q, qn, I.frontier_off.data(), total, op);
-  } else if (lb && lb[0] == 'n') {
-    expand_none_frontier<Op><<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
-                                                             op);
-  } else if (lb && lb[0] == 'w') {
-    expand_wm_frontier<Op><<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
-                                                           op);
-  } else {
-    int nchunks = static_cast<int>((qn + kBlock - 1) / kBlock);
-    expand_cm_frontier<Op><<<std::min(nchunks, kMaxGrid), kBlock, 0, s>>>(
-        view, q, qn, I.frontier_off.data(), op);
-  }
+  launch_expand(I, view, q, qn, I.frontier_off.data(), total, op, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -3461,11 +3489,7 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
                g.v_end, multi,
                DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
                        DevBitmap{I.halo_bm.data()}, cap, view.slice, world_}};
-      if (qn) {
-        int nchunks = static_cast<int>((qn + kBlock - 1) / kBlock);
-        expand_cm_frontier<BfsOp><<<std::min(nchunks, kMaxGrid), kBlock, 0,
-                                    s>>>(view, q.data(), qn, foff.data(), op);
-      }
+      launch_expand(I, view, q.data(), qn, foff.data(), fedges, op, s);
       if (multi) {
         uint64_t nrecv = halo_flush<uint32_t>(I, comm_, rank_, world_,
                                               depth.data(), cap, s);
@@ -3594,17 +3618,15 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
       if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
       gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, nearq[ncur], qn,
                                                         fdeg.data());
-      exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
+      uint64_t fedges =
+          exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
       SsspOp op{dist.data(), prio_hi, DevBitmap{near_bm.data()},
                 DevQueue{farq[fcur], fcnt.data() + fcur},
                 DevBitmap{far_bm.data()}, g.v_begin, g.v_end, multi,
                 DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
                         DevBitmap{I.halo_bm.data()}, cap, view.slice,
                         world_}};
-      int nchunks = static_cast<int>((qn + kBlock - 1) / kBlock);
-      expand_cm_frontier<SsspOp><<<std::min(nchunks, kMaxGrid), kBlock, 0,
-                                   s>>>(view, nearq[ncur], qn, foff.data(),
-                                        op);
+      launch_expand(I, view, nearq[ncur], qn, foff.data(), fedges, op, s);
     }
     if (multi) {
       uint64_t nrecv =

@@ -6,6 +6,7 @@
 // one MI355X GPU == one fragment.
 #pragma once
 
+#include <array>
 #include <cstdint>
 #include <memory>
 #include <vector>
@@ -148,6 +149,10 @@ class GpuContext {
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device
   std::vector<uint64_t> debug_scan(const std::vector<uint32_t>& in);
+  // test hook: frontier-expansion launches so far per scheduler, in the
+  // order cm, wm, strict, none (host-side count; expand_cm_range is no
+  // scheduler choice and is not counted). reset zeroes them after the read.
+  std::array<uint64_t, 4> debug_expand_counts(bool reset = false);
   int device_id() const { return dev_; }
   TcpComm* comm() { return comm_; }
   int rank() const { return rank_; }

@@ -52,6 +52,52 @@ def sssp_oracle(num_v, src, dst, w, source, directed=True):
     return out
 
 
+def sssp_oracle_f32(num_v, src, dst, w, source, directed=True):
+    """Heap Dijkstra in fp32 arithmetic: every sum is np.float32(d + w).
+
+    fp32 addition is monotone in both operands, so this is the minimum over
+    paths of the left-to-right fp32 sum, which is also the fixpoint of any
+    order of fp32 relaxations (the GPU engine's model): bit-exact, not
+    merely close. Multigraph semantics: parallel arcs relax independently;
+    undirected input stores both orientations; self-loops are harmless.
+    Returns float64, DBL_MAX where unreached, as sssp_oracle does.
+    """
+    import heapq
+
+    s = np.asarray(src, dtype=np.int64)
+    d = np.asarray(dst, dtype=np.int64)
+    ww = np.asarray(w, dtype=np.float32)
+    if not directed:
+        s, d, ww = (np.concatenate([s, d]), np.concatenate([d, s]),
+                    np.concatenate([ww, ww]))
+    order = np.argsort(s, kind="stable")
+    s, d, ww = s[order], d[order], ww[order]
+    starts = np.searchsorted(s, np.arange(num_v + 1)).tolist()
+    d = d.tolist()
+    # np.float32 scalars are slow in a Python loop; a Python float holds
+    # every fp32 value exactly, so only the sum is rounded through fp32
+    # (fp64 add then fp32 round equals the fp32 add: 53 >= 2 * 24 + 2)
+    ww = ww.astype(np.float64).tolist()
+    f32 = np.float32
+    inf = float("inf")
+    dist = [inf] * num_v
+    dist[source] = 0.0
+    heap = [(0.0, source)]
+    while heap:
+        du, u = heapq.heappop(heap)
+        if du > dist[u]:
+            continue
+        for k in range(starts[u], starts[u + 1]):
+            nd = float(f32(du + ww[k]))
+            v = d[k]
+            if nd < dist[v]:
+                dist[v] = nd
+                heapq.heappush(heap, (nd, v))
+    out = np.array(dist, dtype=np.float64)
+    out[np.isinf(out)] = DBL_MAX
+    return out
+
+
 def pagerank_oracle(num_v, src, dst, damping=0.85, iters=10, directed=True):
     if not directed:
         src, dst = np.concatenate([src, dst]), np.concatenate([dst, src])
@@ -236,3 +282,60 @@ def kclique_oracle(num_v, src, dst, k, directed=False):
     if k == 2:
         return sum(len(o) for o in oriented)
     return sum(rec(o, 1) for o in oriented if o)
+
+
+def cdlp_oracle_fast(num_v, src, dst, iters=10, directed=True,
+                     return_changed=False):
+    """cdlp_oracle vectorised (sort-based mode with min tie-break), for
+    graphs too large for the per-vertex loop. tests/test_oracles_fast.py
+    holds it equal to cdlp_oracle. With return_changed also returns the
+    number of labels that changed in each iteration."""
+    ns = np.concatenate([src, dst]).astype(np.int64)
+    nd = np.concatenate([dst, src]).astype(np.int64)
+    labels = np.arange(num_v, dtype=np.int64)
+    changed = []
+    for _ in range(iters):
+        key = np.sort(ns * num_v + labels[nd])
+        first = np.ones(len(key), dtype=bool)
+        first[1:] = key[1:] != key[:-1]
+        run_key = key[first]
+        run_cnt = np.diff(np.append(np.flatnonzero(first), len(key)))
+        run_v, run_lab = run_key // num_v, run_key % num_v
+        # per vertex: highest count first, then lowest label
+        order = np.lexsort((run_lab, -run_cnt, run_v))
+        run_v, run_lab = run_v[order], run_lab[order]
+        head = np.ones(len(run_v), dtype=bool)
+        head[1:] = run_v[1:] != run_v[:-1]
+        new = labels.copy()
+        new[run_v[head]] = run_lab[head]
+        changed.append(int((new != labels).sum()))
+        labels = new
+    return (labels, changed) if return_changed else labels
+
+
+def coreness_oracle_fast(num_v, src, dst, directed=False):
+    """coreness_oracle peeled a whole level set at a time. Peeling is
+    monotone, so the batch order gives the same coreness;
+    tests/test_oracles_fast.py holds the two equal."""
+    s = np.asarray(src, dtype=np.int64)
+    d = np.asarray(dst, dtype=np.int64)
+    keep = s != d
+    s, d = s[keep], d[keep]
+    if not directed:
+        s, d = np.concatenate([s, d]), np.concatenate([d, s])
+    rem = np.bincount(s, minlength=num_v).astype(np.int64)
+    core = np.zeros(num_v, dtype=np.int64)
+    alive = np.ones(num_v, bool)
+    k = 0
+    while alive.any():
+        k = max(k, int(rem[alive].min()))
+        while True:
+            peel = alive & (rem <= k)
+            if not peel.any():
+                break
+            core[peel] = k
+            alive[peel] = False
+            hit = peel[s] & alive[d]
+            rem -= np.bincount(d[hit], minlength=num_v)
+        k += 1
+    return core

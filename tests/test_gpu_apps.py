@@ -5,7 +5,7 @@ import pytest
 
 import grapehip
 from oracles import (bfs_oracle, cdlp_oracle, lcc_oracle, pagerank_oracle,
-                     sssp_oracle, wcc_oracle, INT64_MAX)
+                     sssp_oracle_f32, wcc_oracle, INT64_MAX)
 
 pytestmark = pytest.mark.gpu
 
@@ -49,20 +49,23 @@ def test_gpu_sssp(eng):
     src, dst, w = random_graph(weighted=True)
     g = eng.load_edges(src, dst, weights=w, directed=True, num_vertices=5000)
     _, vals = by_oid(eng.sssp(g, 3))
-    expect = sssp_oracle(5000, src, dst, w, 3, directed=True)
-    # fp32 relaxation vs fp64 oracle
+    expect = sssp_oracle_f32(5000, src, dst, w, 3, directed=True)
+    # fp32 relaxation to convergence == fp32 Dijkstra, bit for bit
     finite = expect < 1e300
     assert np.array_equal(vals >= 1e300, ~finite)
-    assert np.allclose(vals[finite], expect[finite], rtol=1e-4)
+    assert np.array_equal(vals[finite].astype(np.float32),
+                          expect[finite].astype(np.float32))
 
 
 def test_gpu_sssp_undirected(eng):
     src, dst, w = random_graph(num_v=3000, num_e=20000, seed=13, weighted=True)
     g = eng.load_edges(src, dst, weights=w, directed=False, num_vertices=3000)
     _, vals = by_oid(eng.sssp(g, 7))
-    expect = sssp_oracle(3000, src, dst, w, 7, directed=False)
+    expect = sssp_oracle_f32(3000, src, dst, w, 7, directed=False)
     finite = expect < 1e300
-    assert np.allclose(vals[finite], expect[finite], rtol=1e-4)
+    assert np.array_equal(vals >= 1e300, ~finite)
+    assert np.array_equal(vals[finite].astype(np.float32),
+                          expect[finite].astype(np.float32))
 
 
 def test_gpu_pagerank(eng):

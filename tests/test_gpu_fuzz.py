@@ -1,7 +1,8 @@
 """GPU seed-sweep fuzz: many random graph shapes x all six kernels vs the
 NumPy oracles, plus the reference's LB-strategy sweep (misc/
 cuda_app_tests.sh runs every app under --lb none|cm|strict — grapehip's
-GRAPEHIP_LB env selects the expansion kernel)."""
+GRAPEHIP_LB env selects the expansion kernel, and the engine's launch
+counters show that it did)."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ import pytest
 
 import grapehip
 from oracles import (bfs_oracle, cdlp_oracle, lcc_oracle, pagerank_oracle,
-                     sssp_oracle, wcc_oracle)
+                     sssp_oracle_f32, wcc_oracle)
 
 REPO = Path(__file__).resolve().parent.parent
 pytestmark = pytest.mark.gpu
@@ -42,11 +43,12 @@ def test_gpu_fuzz_suite(eng, seed):
                           bfs_oracle(nv, src, dst, source, directed=False))
 
     r = eng.sssp(g, source)
-    exp = sssp_oracle(nv, src, dst, w, source, directed=False)
+    exp = sssp_oracle_f32(nv, src, dst, w, source, directed=False)
     got = r["values"][np.argsort(r["oids"])]
     finite = exp < 1e300
-    assert np.allclose(got[finite], exp[finite], rtol=1e-4)
-    assert (got[~finite] > 1e300).all()
+    assert np.array_equal(got[finite].astype(np.float32),
+                          exp[finite].astype(np.float32))
+    assert np.array_equal(got > 1e300, ~finite)
 
     r = eng.pagerank(g, 0.85, 6)
     assert np.allclose(r["values"][np.argsort(r["oids"])],
@@ -84,27 +86,42 @@ dst = rng.integers(0, nv, ne).astype(np.int64)
 w = (rng.random(ne, dtype=np.float32) * 9 + 1)
 eng = grapehip.Engine(rank=0, world=1, master_port=29781, gpu=True)
 g = eng.load_edges(src, dst, weights=w, directed=False, num_vertices=nv)
-b = eng.bfs(g, 3)
-s = eng.sssp(g, 3)
-out = {"bfs": b["values"][np.argsort(b["oids"])].tolist(),
-       "sssp": s["values"][np.argsort(s["oids"])].tolist()}
+counts = {}
+def run(name, fn):
+    before = eng._debug_expand_counts()
+    r = fn()
+    after = eng._debug_expand_counts()
+    counts[name] = {k: after[k] - before[k] for k in after}
+    return r["values"][np.argsort(r["oids"])].tolist()
+out = {"bfs": run("bfs", lambda: eng.bfs(g, 3)),
+       "sssp": run("sssp", lambda: eng.sssp(g, 3)), "counts": counts}
 json.dump(out, open(os.environ["GRAPEHIP_OUT"], "w"))
 '''
+
+LBS = ("cm", "wm", "strict", "none")
 
 
 def test_lb_strategies_agree(tmp_path):
     # np x lb matrix (reference cuda_app_tests.sh): every LB strategy must
-    # produce identical results
+    # produce identical results, with the scheduler asked for and no other.
+    # GRAPEHIP_BFS_PULL_DIV=1 keeps BFS pushing at every level.
     results = {}
-    for lb in ("cm", "strict", "none"):
+    for lb in LBS:
         out = tmp_path / ("lb_%s.json" % lb)
         env = dict(os.environ, GRAPEHIP_REPO=str(REPO),
-                   GRAPEHIP_OUT=str(out), GRAPEHIP_LB=lb)
+                   GRAPEHIP_OUT=str(out), GRAPEHIP_LB=lb,
+                   GRAPEHIP_BFS_PULL_DIV="1")
         r = subprocess.run([sys.executable, "-c", LB_WORKER], env=env,
                            capture_output=True, text=True, timeout=300)
+        # a child that died stops the sweep: nothing more is launched
         assert r.returncode == 0, (lb, r.stdout + r.stderr)
         results[lb] = json.load(open(out))
-    for lb in ("strict", "none"):
+        for app in ("bfs", "sssp"):
+            counts = results[lb]["counts"][app]
+            assert counts[lb] > 0, (lb, app, counts)
+            assert all(counts[o] == 0 for o in LBS if o != lb), (lb, app,
+                                                                 counts)
+    for lb in LBS[1:]:
         assert results[lb]["bfs"] == results["cm"]["bfs"], lb
-        assert np.allclose(results[lb]["sssp"], results["cm"]["sssp"],
-                           rtol=1e-6), lb
+        assert np.array_equal(np.array(results[lb]["sssp"]),
+                              np.array(results["cm"]["sssp"])), lb

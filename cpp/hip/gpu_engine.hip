@@ -605,52 +605,102 @@ __global__ void seg_bigunpad_kernel(const uint64_t* __restrict__ off,
 
 // ===========================================================================
 // CM-style load-balanced edge expansion (LDS-staged owner search).
-// Each block claims 256 consecutive work items (frontier entries or rows),
-// stages their frontier-edge prefix + adjacency base in LDS, then its 256
-// threads sweep the chunk's edges, binary-searching the owner in LDS.
+// Each block stages up to 256 consecutive work items (frontier entries or
+// rows) with their frontier-edge prefix + adjacency base in LDS, then its
+// 256 threads sweep the staged edges, binary-searching the owner in LDS.
 // Reference semantics: cuda/parallel/parallel_engine.h LBCM (:718-771).
 // ===========================================================================
 
+// Default arcs per work item of expand_cm_frontier (GRAPEHIP_EXPAND_TILE
+// overrides; see KERNELS.md "Tiled frontier expansion").
+constexpr uint32_t kExpandTile = 4096;
+
+// Last frontier entry i in [0, qn) with foff[i] <= e, for e < foff[qn]:
+// the entry that owns arc e (entries without an arc repeat their
+// successor's prefix and are never the last). One wave searches 64-ary,
+// so 2^27 entries take five dependent loads, not 27. All 64 lanes call it.
+__device__ __forceinline__ uint32_t wave_owner_search(
+    const uint64_t* __restrict__ foff, uint32_t qn, uint64_t e, int lane) {
+  uint64_t lo = 0, hi = qn;  // foff[lo] <= e; hi == qn or foff[hi] > e
+  while (hi - lo > 1) {
+    const uint64_t step = (hi - lo + 63) >> 6;
+    const uint64_t p = lo + (lane + 1) * step;
+    const bool le = p < hi && foff[p] <= e;
+    // the prefix never decreases: the lanes that hold are lanes 0..cnt-1
+    const int cnt = __popcll(__ballot(le));
+    const uint64_t nlo = lo + cnt * step;
+    const uint64_t nhi = nlo + step;
+    lo = nlo;
+    hi = nhi < hi ? nhi : hi;
+  }
+  return static_cast<uint32_t>(lo);
+}
+
+// Work item = tile of `tile` consecutive arcs of the frontier's arc space
+// [0, total), not a count of entries: ascending-id queues put the heaviest
+// rows first, and entry chunks gave a few blocks most of the arcs. A block
+// finds the entry that owns its tile's first arc, then walks the owners in
+// LDS batches of up to 256, sweeping each batch's arcs clamped to the tile.
+// Every arc of [0, total) goes to op exactly once. Needs total > 0.
 template <typename EdgeOp>
 __global__ void expand_cm_frontier(DevGraphView g, const uint32_t* __restrict__ q,
                                    uint32_t qn, const uint64_t* __restrict__ foff,
-                                   EdgeOp op) {
+                                   uint64_t total, uint32_t tile, EdgeOp op) {
   __shared__ uint64_t s_off[kBlock + 1];   // frontier-space edge prefix
   __shared__ uint64_t s_base[kBlock];      // CSR base of each vertex
   __shared__ uint32_t s_v[kBlock];
+  __shared__ uint32_t s_first;
   const int tid = threadIdx.x;
-  for (uint32_t chunk = blockIdx.x * kBlock; chunk < qn;
-       chunk += gridDim.x * kBlock) {
-    const int n = min(static_cast<uint32_t>(kBlock), qn - chunk);
-    if (tid < n) s_off[tid] = foff[chunk + tid];
-    if (tid == 0) s_off[n] = foff[chunk + n];
-    if (tid < n) {
-      uint32_t v = q[chunk + tid];
-      s_v[tid] = v;
-      s_base[tid] = g.oe_off[g.row(v)];
+  const uint64_t ntiles = (total + tile - 1) / tile;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const uint64_t tile_lo = t * tile;
+    const uint64_t tile_hi = tile_lo + tile < total ? tile_lo + tile : total;
+    if (tid < kWave) {
+      uint32_t first = wave_owner_search(foff, qn, tile_lo, tid);
+      if (tid == 0) s_first = first;
     }
     __syncthreads();
-    const uint64_t e0 = s_off[0], e1 = s_off[n];
-    // a thread's edges are strided, so its owner index only moves forward:
-    // binary-search once, then advance incrementally (amortized O(1) LDS)
-    int lo = 0;
-    {
-      uint64_t e = e0 + tid;
-      if (e < e1) {
-        int hi = n - 1;
-        while (lo < hi) {
-          int mid = (lo + hi + 1) >> 1;
-          if (s_off[mid] <= e) lo = mid; else hi = mid - 1;
+    uint32_t chunk = s_first;
+    for (;;) {
+      const int n = min(static_cast<uint32_t>(kBlock), qn - chunk);
+      if (tid < n) {
+        const uint64_t o = foff[chunk + tid];
+        s_off[tid] = o;
+        // entries at or past the tile's end own none of its arcs
+        if (o < tile_hi) {
+          uint32_t v = q[chunk + tid];
+          s_v[tid] = v;
+          s_base[tid] = g.oe_off[g.row(v)];
         }
       }
+      if (tid == 0) s_off[n] = foff[chunk + n];
+      __syncthreads();
+      const uint64_t batch_end = s_off[n];
+      const uint64_t e0 = s_off[0] > tile_lo ? s_off[0] : tile_lo;
+      const uint64_t e1 = batch_end < tile_hi ? batch_end : tile_hi;
+      // a thread's edges are strided, so its owner index only moves forward:
+      // binary-search once, then advance incrementally (amortized O(1) LDS)
+      int lo = 0;
+      {
+        uint64_t e = e0 + tid;
+        if (e < e1) {
+          int hi = n - 1;
+          while (lo < hi) {
+            int mid = (lo + hi + 1) >> 1;
+            if (s_off[mid] <= e) lo = mid; else hi = mid - 1;
+          }
+        }
+      }
+      for (uint64_t e = e0 + tid; e < e1; e += blockDim.x) {
+        while (lo + 1 < n && s_off[lo + 1] <= e) ++lo;
+        const uint32_t u = s_v[lo];
+        const uint64_t eid = s_base[lo] + (e - s_off[lo]);
+        op(u, g.oe_dst[eid], g.oe_w ? g.oe_w[eid] : 1.0f);
+      }
+      __syncthreads();
+      if (batch_end >= tile_hi || chunk + n >= qn) break;
+      chunk += n;
     }
-    for (uint64_t e = e0 + tid; e < e1; e += blockDim.x) {
-      while (lo + 1 < n && s_off[lo + 1] <= e) ++lo;
-      const uint32_t u = s_v[lo];
-      const uint64_t eid = s_base[lo] + (e - s_off[lo]);
-      op(u, g.oe_dst[eid], g.oe_w ? g.oe_w[eid] : 1.0f);
-    }
-    __syncthreads();
   }
 }
 
@@ -2275,9 +2325,19 @@ struct GpuContext::Impl {
   // frontier scratch
   DeviceBuffer<uint32_t> frontier_deg;
   DeviceBuffer<uint64_t> frontier_off;
+  // traversal workspace of bfs()/sssp(): grows, never shrinks, freed with
+  // the context. Both apps share it and initialise what they use inside
+  // their timed region; a call on a smaller graph uses a prefix.
+  DeviceBuffer<uint32_t> trav_state;   // BFS depth / SSSP distance bits
+  DeviceBuffer<uint32_t> trav_q[4];    // [0] BFS queue; SSSP near/far pairs
+  DeviceBuffer<uint32_t> trav_near_bm, trav_far_bm;
+  DeviceBuffer<unsigned long long> trav_fcnt;  // SSSP far queue counters
+  DeviceBuffer<uint32_t> trav_fdeg;    // frontier degrees (separate from the
+  DeviceBuffer<uint64_t> trav_foff;    //  compaction scratch above)
   double t_exchange = 0;
-  // host-side count of frontier-expansion launches per scheduler
-  // (launch_expand only; test hook, see debug_expand_counts)
+  // host-side count of frontier expansions dispatched per scheduler
+  // (launch_expand only, a frontier without an arc included; test hook,
+  // see debug_expand_counts)
   uint64_t expand_counts[kLbCount] = {0, 0, 0, 0};
 };
 
@@ -2308,6 +2368,12 @@ uint32_t padded_nv(const DeviceGraph& g, int world) {
                                          : g.nv_global;
   uint64_t pad = static_cast<uint64_t>(slice) * world;
   return static_cast<uint32_t>(pad > g.nv_global ? pad : g.nv_global);
+}
+
+// grow-only resize: contents are not kept
+template <typename T>
+void grow(DeviceBuffer<T>& b, size_t n) {
+  if (b.size() < n) b.resize(n);
 }
 
 double wall_s() {
@@ -3366,9 +3432,21 @@ void launch_expand(GpuContext::Impl& I, const DevGraphView& view,
                                                            op);
   } else {
     ++I.expand_counts[kLbCm];
-    int nchunks = static_cast<int>((qn + kBlock - 1) / kBlock);
-    expand_cm_frontier<Op><<<std::min(nchunks, kMaxGrid), kBlock, 0, s>>>(
-        view, q, qn, offsets, op);
+    // arcs per tile: read once per process, like GRAPEHIP_LB
+    static const uint32_t tile = [] {
+      const char* e = getenv("GRAPEHIP_EXPAND_TILE");
+      if (!e) return kExpandTile;
+      long v = atol(e);
+      if (v < kBlock || v % kBlock != 0 || v > (1l << 30))
+        throw std::runtime_error(
+            "GRAPEHIP_EXPAND_TILE must be a multiple of 256, at least 256");
+      return static_cast<uint32_t>(v);
+    }();
+    if (total == 0) return;  // a frontier of sinks: nothing to launch
+    const uint64_t ntiles = (total + tile - 1) / tile;
+    expand_cm_frontier<Op>
+        <<<static_cast<int>(std::min<uint64_t>(ntiles, kMaxGrid)), kBlock, 0,
+           s>>>(view, q, qn, offsets, total, tile, op);
   }
 }
 
@@ -3407,12 +3485,17 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
   const uint64_t* pull_off = !g.directed ? g.oe_off.data() : g.ie_off.data();
   const uint32_t* pull_dst = !g.directed ? g.oe_dst.data() : g.ie_dst.data();
 
-  DeviceBuffer<uint32_t> depth(nv_pad);
-  DeviceBuffer<uint32_t> q(owned + 64);
+  // context workspace, shared with sssp(): no allocation after the first
+  // call on the largest graph
   size_t bm_words = (static_cast<size_t>(owned) + 31) / 32 + 1;
-  DeviceBuffer<uint32_t> next_bm(bm_words);
-  DeviceBuffer<uint32_t> fdeg;   // frontier degrees (separate from compaction
-  DeviceBuffer<uint64_t> foff;   //  scratch so both stay live in one round)
+  grow(I.trav_state, nv_pad);
+  grow(I.trav_q[0], static_cast<size_t>(owned) + 64);
+  grow(I.trav_near_bm, bm_words);
+  uint32_t* const depth = I.trav_state.data();
+  uint32_t* const q = I.trav_q[0].data();
+  uint32_t* const next_bm = I.trav_near_bm.data();
+  DeviceBuffer<uint32_t>& fdeg = I.trav_fdeg;
+  DeviceBuffer<uint64_t>& foff = I.trav_foff;
   if (multi) {
     I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
     I.halo_cnt.resize(world_);
@@ -3424,19 +3507,20 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
   double t0 = wall_s();
   const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
 
-  depth.fill_bytes(0xFF, s);
-  next_bm.zero(s);
+  if (nv_pad)
+    HIP_CHECK(hipMemsetAsync(depth, 0xFF, static_cast<size_t>(nv_pad) * 4, s));
+  HIP_CHECK(hipMemsetAsync(next_bm, 0, bm_words * 4, s));
   if (multi) {
     I.halo_cnt.zero(s);
     I.halo_bm.zero(s);
   }
   uint32_t src = map_source(g, source, s);
   if (src >= g.v_begin && src < g.v_end)
-    bfs_seed_kernel<<<1, 1, 0, s>>>(depth.data(), src, g.v_begin,
-                                    next_bm.data());
+    bfs_seed_kernel<<<1, 1, 0, s>>>(depth, src, g.v_begin,
+                                    next_bm);
   uint32_t qn =
-      static_cast<uint32_t>(compact_frontier(I, next_bm.data(), owned,
-                                             g.v_begin, q.data(), s));
+      static_cast<uint32_t>(compact_frontier(I, next_bm, owned,
+                                             g.v_begin, q, s));
   uint64_t global_curr = multi ? comm_->allreduce_sum(qn) : qn;
   uint32_t level = 0;
   int rounds = 0;
@@ -3453,7 +3537,7 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
     if (qn) {
       if (fdeg.size() < qn) fdeg.resize(qn + (qn >> 2) + 64);
       if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
-      gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, q.data(), qn,
+      gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
                                                         fdeg.data());
       fedges = exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
     }
@@ -3465,45 +3549,45 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
       if (multi) {
         // refresh referenced remote depths only (vs allgathering every
         // slice): the pull scan reads depth[dst] for local dsts alone
-        mirror_sync_begin(I, g, depth.data(), s);
-        mirror_sync_end(I, g, depth.data(), s);
+        mirror_sync_begin(I, g, depth, s);
+        mirror_sync_end(I, g, depth, s);
       }
-      DevBitmap nb{next_bm.data()};
+      DevBitmap nb{next_bm};
       if (g.n_small)
         bfs_pull_small_kernel<<<grid_for(g.n_small), kBlock, 0, s>>>(
             pull_off, pull_dst, g.rows_small.data(), g.n_small, g.v_begin,
-            depth.data(), level, nb);
+            depth, level, nb);
       if (g.n_mid)
         bfs_pull_mid_kernel<<<grid_for(g.n_mid * kWave), kBlock, 0, s>>>(
             pull_off, pull_dst, g.rows_mid.data(), g.n_mid, g.v_begin,
-            depth.data(), level, nb);
+            depth, level, nb);
       if (g.n_large)
         bfs_pull_large_kernel<<<static_cast<int>(std::min<uint64_t>(
                                     std::max<uint64_t>(g.n_large, 1),
                                     kMaxGrid)),
                                 kBlock, 0, s>>>(
             pull_off, pull_dst, g.rows_large.data(), g.n_large, g.v_begin,
-            depth.data(), level, nb);
+            depth, level, nb);
     } else {
-      BfsOp op{depth.data(), level + 1, DevBitmap{next_bm.data()}, g.v_begin,
+      BfsOp op{depth, level + 1, DevBitmap{next_bm}, g.v_begin,
                g.v_end, multi,
                DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
                        DevBitmap{I.halo_bm.data()}, cap, view.slice, world_}};
-      launch_expand(I, view, q.data(), qn, foff.data(), fedges, op, s);
+      launch_expand(I, view, q, qn, foff.data(), fedges, op, s);
       if (multi) {
         uint64_t nrecv = halo_flush<uint32_t>(I, comm_, rank_, world_,
-                                              depth.data(), cap, s);
+                                              depth, cap, s);
         if (nrecv)
           halo_process_kernel<uint32_t, BfsRecvOp>
               <<<grid_for(nrecv), kBlock, 0, s>>>(
                   reinterpret_cast<HaloPair<uint32_t>*>(I.recvbuf.data()),
                   nrecv,
-                  BfsRecvOp{depth.data(), DevBitmap{next_bm.data()},
+                  BfsRecvOp{depth, DevBitmap{next_bm},
                             g.v_begin});
       }
     }
-    qn = static_cast<uint32_t>(compact_frontier(I, next_bm.data(), owned,
-                                                g.v_begin, q.data(), s));
+    qn = static_cast<uint32_t>(compact_frontier(I, next_bm, owned,
+                                                g.v_begin, q, s));
     global_curr = multi ? comm_->allreduce_sum(qn) : qn;
     if (getenv("GRAPEHIP_DEBUG"))
       fprintf(stderr, "[bfs] level=%u mode=%s fedges=%lu next=%u t=%.1fms\n",
@@ -3524,7 +3608,7 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
   res.traversed_edges = g.input_edges;
   if (fetch) {
     std::vector<uint32_t> d32(owned);
-    HIP_CHECK(hipMemcpyAsync(d32.data(), depth.data() + g.v_begin, owned * 4,
+    HIP_CHECK(hipMemcpyAsync(d32.data(), depth + g.v_begin, owned * 4,
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     res.i64.resize(owned);
@@ -3550,15 +3634,22 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
   uint64_t cap = view.slice;
   bool multi = world_ > 1;
 
-  DeviceBuffer<float> dist(nv_pad);
-  DeviceBuffer<uint32_t> q0(owned + 64), q1(owned + 64);   // near dbl-buf
-  DeviceBuffer<uint32_t> qf0(owned + 64), qf1(owned + 64);  // far dbl-buf
-  DeviceBuffer<unsigned long long> fcnt(2);  // far queue counters
+  // context workspace, shared with bfs(): no allocation after the first
+  // call on the largest graph
   size_t own_words = (static_cast<size_t>(owned) + 31) / 32 + 1;
   uint64_t glob_words = (static_cast<uint64_t>(nv_pad) + 31) / 32;
-  DeviceBuffer<uint32_t> near_bm(own_words), far_bm(glob_words);
-  DeviceBuffer<uint32_t> fdeg;
-  DeviceBuffer<uint64_t> foff;
+  grow(I.trav_state, nv_pad);
+  for (auto& b : I.trav_q)  // near and far queues, double-buffered
+    grow(b, static_cast<size_t>(owned) + 64);
+  grow(I.trav_fcnt, 2);
+  grow(I.trav_near_bm, own_words);
+  grow(I.trav_far_bm, glob_words);
+  float* const dist = reinterpret_cast<float*>(I.trav_state.data());
+  unsigned long long* const fcnt = I.trav_fcnt.data();
+  uint32_t* const near_bm = I.trav_near_bm.data();
+  uint32_t* const far_bm = I.trav_far_bm.data();
+  DeviceBuffer<uint32_t>& fdeg = I.trav_fdeg;
+  DeviceBuffer<uint64_t>& foff = I.trav_foff;
   if (multi) {
     I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
     I.halo_cnt.resize(world_);
@@ -3589,40 +3680,40 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
   double t0 = wall_s();
   const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
 
-  fill(dist.data(), std::numeric_limits<float>::max(), nv_pad, s);
-  fcnt.zero(s);
-  near_bm.zero(s);
-  far_bm.zero(s);
+  fill(dist, std::numeric_limits<float>::max(), nv_pad, s);
+  HIP_CHECK(hipMemsetAsync(fcnt, 0, 2 * sizeof(unsigned long long), s));
+  HIP_CHECK(hipMemsetAsync(near_bm, 0, own_words * 4, s));
+  if (glob_words) HIP_CHECK(hipMemsetAsync(far_bm, 0, glob_words * 4, s));
   if (multi) {
     I.halo_cnt.zero(s);
     I.halo_bm.zero(s);
   }
   uint32_t src = map_source(g, source, s);
   if (src >= g.v_begin && src < g.v_end)
-    sssp_seed_kernel<<<1, 1, 0, s>>>(dist.data(), src, g.v_begin,
-                                     near_bm.data());
-  uint32_t* nearq[2] = {q0.data(), q1.data()};
-  uint32_t* farq[2] = {qf0.data(), qf1.data()};
+    sssp_seed_kernel<<<1, 1, 0, s>>>(dist, src, g.v_begin,
+                                     near_bm);
+  uint32_t* nearq[2] = {I.trav_q[0].data(), I.trav_q[1].data()};
+  uint32_t* farq[2] = {I.trav_q[2].data(), I.trav_q[3].data()};
   int ncur = 0, fcur = 0;
   float prio = 0.0f;
   int rounds = 0;
   unsigned long long zero = 0;
   std::vector<unsigned long long> hfc(2);
   uint32_t qn = static_cast<uint32_t>(compact_frontier(
-      I, near_bm.data(), owned, g.v_begin, nearq[ncur], s));
+      I, near_bm, owned, g.v_begin, nearq[ncur], s));
   uint64_t g_near = multi ? comm_->allreduce_sum(qn) : qn;
   for (;;) {
     float prio_hi = prio + delta;
+    uint64_t fedges = 0;
     if (qn) {
       if (fdeg.size() < qn) fdeg.resize(qn + (qn >> 2) + 64);
       if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
       gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, nearq[ncur], qn,
                                                         fdeg.data());
-      uint64_t fedges =
-          exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
-      SsspOp op{dist.data(), prio_hi, DevBitmap{near_bm.data()},
-                DevQueue{farq[fcur], fcnt.data() + fcur},
-                DevBitmap{far_bm.data()}, g.v_begin, g.v_end, multi,
+      fedges = exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
+      SsspOp op{dist, prio_hi, DevBitmap{near_bm},
+                DevQueue{farq[fcur], fcnt + fcur},
+                DevBitmap{far_bm}, g.v_begin, g.v_end, multi,
                 DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
                         DevBitmap{I.halo_bm.data()}, cap, view.slice,
                         world_}};
@@ -3630,27 +3721,29 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
     }
     if (multi) {
       uint64_t nrecv =
-          halo_flush<float>(I, comm_, rank_, world_, dist.data(), cap, s);
+          halo_flush<float>(I, comm_, rank_, world_, dist, cap, s);
       if (nrecv)
         halo_process_kernel<float, SsspRecvOp>
             <<<grid_for(nrecv), kBlock, 0, s>>>(
                 reinterpret_cast<HaloPair<float>*>(I.recvbuf.data()), nrecv,
-                SsspRecvOp{dist.data(), prio_hi, DevBitmap{near_bm.data()},
-                           DevQueue{farq[fcur], fcnt.data() + fcur},
-                           DevBitmap{far_bm.data()}, g.v_begin});
+                SsspRecvOp{dist, prio_hi, DevBitmap{near_bm},
+                           DevQueue{farq[fcur], fcnt + fcur},
+                           DevBitmap{far_bm}, g.v_begin});
     }
     ++rounds;
     uint32_t next_qn = static_cast<uint32_t>(compact_frontier(
-        I, near_bm.data(), owned, g.v_begin, nearq[1 - ncur], s));
+        I, near_bm, owned, g.v_begin, nearq[1 - ncur], s));
     g_near = multi ? comm_->allreduce_sum(next_qn) : next_qn;
     if (getenv("GRAPEHIP_DEBUG"))
-      fprintf(stderr, "[sssp] round=%d prio=%.0f in=%u next=%u t=%.1fms\n",
-              rounds, prio, qn, next_qn, (wall_s() - t0) * 1e3);
+      fprintf(stderr,
+              "[sssp] round=%d prio=%.0f in=%u fedges=%lu next=%u t=%.1fms\n",
+              rounds, prio, qn, (unsigned long)fedges, next_qn,
+              (wall_s() - t0) * 1e3);
     ncur = 1 - ncur;
     qn = next_qn;
     if (g_near > 0) continue;
     // near exhausted globally: advance priority, repartition far buckets
-    HIP_CHECK(hipMemcpyAsync(hfc.data(), fcnt.data(), 16,
+    HIP_CHECK(hipMemcpyAsync(hfc.data(), fcnt, 16,
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     uint64_t far_n = hfc[fcur];
@@ -3661,16 +3754,16 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
       float new_hi = prio + delta;
       if (far_n)
         sssp_repart_kernel<<<grid_for(far_n), kBlock, 0, s>>>(
-            farq[fcur], static_cast<uint32_t>(far_n), dist.data(), new_hi,
-            DevBitmap{near_bm.data()}, g.v_begin,
-            DevQueue{farq[1 - fcur], fcnt.data() + (1 - fcur)},
-            DevBitmap{far_bm.data()});
-      HIP_CHECK(hipMemcpyAsync(fcnt.data() + fcur, &zero, 8,
+            farq[fcur], static_cast<uint32_t>(far_n), dist, new_hi,
+            DevBitmap{near_bm}, g.v_begin,
+            DevQueue{farq[1 - fcur], fcnt + (1 - fcur)},
+            DevBitmap{far_bm});
+      HIP_CHECK(hipMemcpyAsync(fcnt + fcur, &zero, 8,
                                hipMemcpyHostToDevice, s));
       qn = static_cast<uint32_t>(compact_frontier(
-          I, near_bm.data(), owned, g.v_begin, nearq[ncur], s));
+          I, near_bm, owned, g.v_begin, nearq[ncur], s));
       g_near = multi ? comm_->allreduce_sum(qn) : qn;
-      HIP_CHECK(hipMemcpyAsync(hfc.data(), fcnt.data(), 16,
+      HIP_CHECK(hipMemcpyAsync(hfc.data(), fcnt, 16,
                                hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       fcur = 1 - fcur;
@@ -3691,7 +3784,7 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
   res.traversed_edges = g.input_edges;
   if (fetch) {
     std::vector<float> d32(owned);
-    HIP_CHECK(hipMemcpyAsync(d32.data(), dist.data() + g.v_begin, owned * 4,
+    HIP_CHECK(hipMemcpyAsync(d32.data(), dist + g.v_begin, owned * 4,
                              hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
     res.f64.resize(owned);

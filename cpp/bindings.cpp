@@ -816,11 +816,33 @@ PYBIND11_MODULE(_core, m) {
            },
            py::arg("graph"), py::arg("values") = true)
       .def("bc",
-           [](PyEngine& eng, PyGraph& g, int64_t source) {
+           [](PyEngine& eng, PyGraph& g, int64_t source, bool values) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (eng.use_gpu && g.dev) {
+               GpuRunResult r;
+               {
+                 py::gil_scoped_release rel;
+                 r = eng.gpu->bc(*g.dev, dev_id_map(g).to_dev(source),
+                                 values);
+               }
+               py::dict out = gpu_dict(r, g, /*is_i64=*/false, values);
+               if (values) {
+                 // same rows as "values": real vertices lead the owned range
+                 size_t n = py::len(out["oids"]);
+                 py::array_t<double> sig(n);
+                 std::memcpy(sig.mutable_data(), r.f64b.data(), n * 8);
+                 py::array_t<int64_t> dep(n);
+                 std::memcpy(dep.mutable_data(), r.i64.data(), n * 8);
+                 out["path_num"] = sig;
+                 out["depth"] = dep;
+               }
+               return out;
+             }
+#endif
+             (void)values;  // the host path always returns them
              if (!g.frag)
                throw std::runtime_error(
-                   "bc runs on the CPU engine and needs a host fragment "
-                   "(load with load_edges)");
+                   "bc needs a host fragment (load with load_edges)");
              BCApp app;
              BCContext ctx;
              MessageManager mm;
@@ -842,7 +864,8 @@ PYBIND11_MODULE(_core, m) {
              meta["depth"] = to_np(dep);
              return meta;
            },
-           py::arg("graph"), py::arg("source") = 0)
+           py::arg("graph"), py::arg("source") = 0,
+           py::arg("values") = true)
       .def("kcore",
            [](PyEngine& eng, PyGraph& g, int k, bool values) {
 #ifdef GRAPEHIP_WITH_HIP

@@ -12,8 +12,11 @@
 //   * cuda apps bfs/sssp/pagerank/wcc -> drivers below
 //   * examples/analytical_apps/kcore/kcore.h and core_decomposition/
 //     core_decomposition.h (CPU only in the reference) -> frontier peeling
+//   * examples/analytical_apps/bc/staged_bc{,_bfs}.h (CPU only in the
+//     reference) -> push BFS with path counts + level-queue replay
 #include "gpu_engine.hpp"
 
+#include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 #include <rccl/rccl.h>
 
 #include <algorithm>
@@ -1019,6 +1022,117 @@ __global__ void bfs_seed_kernel(uint32_t* depth, uint32_t src,
     depth[src] = 0;
     uint32_t r = src - v_begin;
     bm_words[r >> 5] |= 1u << (r & 31);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Betweenness centrality (single-source Brandes; cpp/apps/bc.hpp semantics).
+// depth/sigma/acc are indexed by global vid. Owned entries hold the vertex's
+// state; on several ranks the remote entries of sigma and acc hold this
+// rank's pending contributions, zero between halo flushes. The fp64 adds
+// are the hardware atomic (hipMalloc memory only).
+// ---------------------------------------------------------------------------
+
+// Forward arc v->u at level next_depth - 1. Every arc from the previous
+// level into a vertex first reached at next_depth adds the tail's path
+// count; the one that lowered the depth also queues the vertex. sigma[v]
+// was completed by the previous level's launch.
+struct BcFwdOp {
+  uint32_t* depth;
+  double* sigma;
+  uint32_t next_depth;
+  DevBitmap next_bm;  // over owned bits
+  uint32_t v_begin, v_end;
+  bool multi;
+  DevHalo halo;
+  __device__ __forceinline__ void operator()(uint32_t v, uint32_t u,
+                                             float) const {
+    // cheap cached read first: settled vertices (self-loops among them)
+    if (depth[u] < next_depth) return;
+    const bool own = u >= v_begin && u < v_end;
+    if (!own && !multi) return;
+    uint32_t old = atomicMin(&depth[u], next_depth);
+    if (old < next_depth) return;
+    unsafeAtomicAdd(&sigma[u], sigma[v]);
+    if (own) {
+      if (old > next_depth) next_bm.set_once(u - v_begin);
+    } else {
+      halo.add(u);
+    }
+  }
+};
+
+// incoming (v, path count) of the level being expanded — v owned here. The
+// owner applies the sender's rule: a sender's depth copy is an upper bound,
+// so a pair for a vertex that is already shallower is dropped.
+struct BcFwdRecvOp {
+  uint32_t* depth;
+  double* sigma;
+  uint32_t next_depth;
+  DevBitmap next_bm;
+  uint32_t v_begin;
+  __device__ __forceinline__ void operator()(uint32_t v, double sig) const {
+    if (depth[v] < next_depth) return;
+    uint32_t old = atomicMin(&depth[v], next_depth);
+    if (old < next_depth) return;
+    unsafeAtomicAdd(&sigma[v], sig);
+    if (old > next_depth) next_bm.set_once(v - v_begin);
+  }
+};
+
+// Backward arc v->u, v at depth up_depth + 1: push v's coefficient to the
+// shallower end (the reference's out-adjacency rule, directed or not).
+struct BcBackOp {
+  const uint32_t* depth;
+  const double* coef;  // by owned row
+  double* acc;
+  uint32_t up_depth;
+  uint32_t v_begin, v_end;
+  bool multi;
+  DevHalo halo;
+  __device__ __forceinline__ void operator()(uint32_t v, uint32_t u,
+                                             float) const {
+    if (depth[u] != up_depth) return;
+    const bool own = u >= v_begin && u < v_end;
+    if (!own && !multi) return;
+    unsafeAtomicAdd(&acc[u], coef[v - v_begin]);
+    if (!own) halo.add(u);
+  }
+};
+
+struct BcBackRecvOp {  // incoming (v, coefficient sum) — v owned here
+  double* acc;
+  __device__ __forceinline__ void operator()(uint32_t v, double c) const {
+    unsafeAtomicAdd(&acc[v], c);  // several peers may send the same v
+  }
+};
+
+__global__ void bc_seed_kernel(uint32_t* depth, double* sigma, uint32_t src,
+                               uint32_t v_begin, uint32_t* bm_words) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    depth[src] = 0;
+    sigma[src] = 1.0;
+    uint32_t r = src - v_begin;
+    bm_words[r >> 5] |= 1u << (r & 31);
+  }
+}
+
+// One level's slice of the order array, after every deeper level has been
+// expanded: delta = sigma * acc (kept in acc) and the coefficient the
+// level's arcs push upwards. sigma >= 1 for every queued vertex.
+__global__ void bc_finalize_kernel(const uint32_t* __restrict__ q,
+                                   uint32_t qn, uint32_t v_begin,
+                                   const double* __restrict__ sigma,
+                                   double* __restrict__ acc,
+                                   double* __restrict__ coef) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < qn;
+       i += stride) {
+    uint32_t v = q[i];
+    double s = sigma[v];
+    double dl = s * acc[v];
+    acc[v] = dl;
+    coef[v - v_begin] = (1.0 + dl) / s;
   }
 }
 
@@ -2334,6 +2448,11 @@ struct GpuContext::Impl {
   DeviceBuffer<unsigned long long> trav_fcnt;  // SSSP far queue counters
   DeviceBuffer<uint32_t> trav_fdeg;    // frontier degrees (separate from the
   DeviceBuffer<uint64_t> trav_foff;    //  compaction scratch above)
+  // bc() fp64 workspace, grow-only like the above: path counts and
+  // dependency sums by global vid, push coefficients by owned row. bc()
+  // also uses trav_state (depth), trav_q[0] (the level-order array),
+  // trav_near_bm and trav_fdeg/trav_foff.
+  DeviceBuffer<double> bc_sigma, bc_acc, bc_coef;
   double t_exchange = 0;
   // host-side count of frontier expansions dispatched per scheduler
   // (launch_expand only, a frontier without an arc included; test hook,
@@ -7172,6 +7291,181 @@ GpuRunResult GpuContext::kcore(DeviceGraph& g, int k, bool fetch) {
 GpuRunResult GpuContext::core_decomposition(DeviceGraph& g, bool fetch) {
   RangeMarker _mk("grapehip::core_decomposition");
   return peel(g, /*all_levels=*/true, 0, fetch);
+}
+
+// ---------------------------------------------------------------------------
+// Betweenness centrality, single source (functors in the app-functor section
+// above). Reference parity: examples/analytical_apps/bc/staged_bc{,_bfs}.h
+// through cpp/apps/bc.hpp.
+//
+// Forward: push-only level-synchronous BFS through launch_expand (GRAPEHIP_LB
+// applies). Each level's frontier is compacted into the next slice of one
+// owned-size order array; the slice offsets stay on the host. Backward: the
+// slices are replayed deepest first, a finalise kernel and one
+// expand_frontier per level, so a single rank reads nothing back.
+// Multi-rank: contributions to remote vertices sit in the remote entries of
+// sigma / acc and travel as (v, fp64) take-and-zero halo pairs, one flush per
+// level in each direction; every rank runs every flush. After the forward
+// pass the remote depth copies are upper bounds only (the level at which this
+// rank first reached the vertex), so one mirror refresh brings the owners'
+// depths before the backward test depth[u] == d - 1 reads them.
+// ---------------------------------------------------------------------------
+GpuRunResult GpuContext::bc(DeviceGraph& g, int64_t source, bool fetch) {
+  RangeMarker _mk("grapehip::bc");
+  static_assert(sizeof(HaloPair<double>) == 16,
+                "fp64 halo pairs pack at a 16-byte stride");
+  auto& I = *impl_;
+  hipStream_t s = I.compute;
+  DevGraphView view = make_view(g, rank_, world_);
+  uint32_t nv_pad = padded_nv(g, world_);
+  uint32_t owned = g.owned();
+  uint64_t cap = view.slice;
+  bool multi = world_ > 1;
+
+  if (multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
+
+  size_t bm_words = (static_cast<size_t>(owned) + 31) / 32 + 1;
+  grow(I.trav_state, nv_pad);
+  grow(I.trav_q[0], static_cast<size_t>(owned) + 64);
+  grow(I.trav_near_bm, bm_words);
+  grow(I.bc_sigma, nv_pad);
+  grow(I.bc_acc, nv_pad);
+  grow(I.bc_coef, static_cast<size_t>(owned) + 1);
+  uint32_t* const depth = I.trav_state.data();
+  uint32_t* const order = I.trav_q[0].data();
+  uint32_t* const next_bm = I.trav_near_bm.data();
+  double* const sigma = I.bc_sigma.data();
+  double* const acc = I.bc_acc.data();
+  double* const coef = I.bc_coef.data();
+  DeviceBuffer<uint32_t>& fdeg = I.trav_fdeg;
+  DeviceBuffer<uint64_t>& foff = I.trav_foff;
+  if (multi) {
+    I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
+    I.halo_cnt.resize(world_);
+    I.halo_bm.resize((static_cast<uint64_t>(nv_pad) + 31) / 32);
+  }
+  const DevHalo halo{I.halo_idx.data(), I.halo_cnt.data(),
+                     DevBitmap{I.halo_bm.data()}, cap, view.slice, world_};
+
+  if (comm_) comm_->barrier();
+  HIP_CHECK(hipDeviceSynchronize());
+  double t0 = wall_s();
+  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+
+  if (nv_pad) {
+    HIP_CHECK(hipMemsetAsync(depth, 0xFF, static_cast<size_t>(nv_pad) * 4, s));
+    HIP_CHECK(hipMemsetAsync(sigma, 0, static_cast<size_t>(nv_pad) * 8, s));
+    HIP_CHECK(hipMemsetAsync(acc, 0, static_cast<size_t>(nv_pad) * 8, s));
+  }
+  HIP_CHECK(hipMemsetAsync(next_bm, 0, bm_words * 4, s));
+  if (multi) {
+    I.halo_cnt.zero(s);
+    I.halo_bm.zero(s);
+  }
+  uint32_t src = map_source(g, source, s);
+  if (src >= g.v_begin && src < g.v_end)
+    bc_seed_kernel<<<1, 1, 0, s>>>(depth, sigma, src, g.v_begin, next_bm);
+
+  // level_off[d] .. level_off[d + 1]: level d's slice of the order array.
+  // Every owned vertex enters one frontier, so the slices fit in `owned`.
+  std::vector<uint64_t> level_off{0};
+  uint32_t qn = static_cast<uint32_t>(
+      compact_frontier(I, next_bm, owned, g.v_begin, order, s));
+  uint64_t global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+  uint32_t level = 0;
+  while (global_curr > 0) {
+    const uint32_t* q = order + level_off.back();
+    level_off.push_back(level_off.back() + qn);
+    uint64_t fedges = 0;
+    if (qn) {
+      if (fdeg.size() < qn) fdeg.resize(qn + (qn >> 2) + 64);
+      if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
+      gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
+                                                        fdeg.data());
+      fedges = exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
+    }
+    launch_expand(I, view, q, qn, foff.data(), fedges,
+                  BcFwdOp{depth, sigma, level + 1, DevBitmap{next_bm},
+                          g.v_begin, g.v_end, multi, halo},
+                  s);
+    if (multi) {
+      uint64_t nrecv = halo_flush<double, true>(I, comm_, rank_, world_,
+                                                sigma, cap, s);
+      if (nrecv)
+        halo_process_kernel<double, BcFwdRecvOp>
+            <<<grid_for(nrecv), kBlock, 0, s>>>(
+                reinterpret_cast<HaloPair<double>*>(I.recvbuf.data()), nrecv,
+                BcFwdRecvOp{depth, sigma, level + 1, DevBitmap{next_bm},
+                            g.v_begin});
+    }
+    qn = static_cast<uint32_t>(compact_frontier(
+        I, next_bm, owned, g.v_begin, order + level_off.back(), s));
+    global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+    if (getenv("GRAPEHIP_DEBUG"))
+      fprintf(stderr, "[bc] fwd level=%u fedges=%lu next=%u t=%.1fms\n",
+              level, (unsigned long)fedges, qn, (wall_s() - t0) * 1e3);
+    ++level;
+  }
+  const int levels = static_cast<int>(level);
+
+  if (multi && levels > 1) {
+    mirror_sync_begin(I, g, depth, s);
+    mirror_sync_end(I, g, depth, s);
+  }
+  for (int d = levels - 1; d >= 0; --d) {
+    const uint32_t* q = order + level_off[d];
+    const uint32_t n = static_cast<uint32_t>(level_off[d + 1] - level_off[d]);
+    if (n)
+      bc_finalize_kernel<<<grid_for(n), kBlock, 0, s>>>(q, n, g.v_begin,
+                                                        sigma, acc, coef);
+    if (d == 0) break;  // the source has nothing above it
+    expand_frontier(I, view, q, n,
+                    BcBackOp{depth, coef, acc, static_cast<uint32_t>(d - 1),
+                             g.v_begin, g.v_end, multi, halo},
+                    s);
+    if (multi) {
+      uint64_t nrecv =
+          halo_flush<double, true>(I, comm_, rank_, world_, acc, cap, s);
+      if (nrecv)
+        halo_process_kernel<double, BcBackRecvOp>
+            <<<grid_for(nrecv), kBlock, 0, s>>>(
+                reinterpret_cast<HaloPair<double>*>(I.recvbuf.data()), nrecv,
+                BcBackRecvOp{acc});
+    }
+    if (getenv("GRAPEHIP_DEBUG"))
+      fprintf(stderr, "[bc] back level=%d slice=%u t=%.1fms\n", d, n,
+              (wall_s() - t0) * 1e3);
+  }
+  HIP_CHECK(hipDeviceSynchronize());
+  if (comm_) comm_->barrier();
+  double t1 = wall_s();
+
+  GpuRunResult res;
+  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
+  res.bytes_coll = I.dc.bytes_coll - b_coll0;
+  res.rounds = levels;
+  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
+  res.traversed_edges = g.input_edges;
+  if (fetch) {
+    std::vector<uint32_t> d32(owned);
+    res.f64.resize(owned);
+    res.f64b.resize(owned);
+    if (owned) {
+      HIP_CHECK(hipMemcpyAsync(d32.data(), depth + g.v_begin, owned * 4ull,
+                               hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(res.f64.data(), acc + g.v_begin, owned * 8ull,
+                               hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipMemcpyAsync(res.f64b.data(), sigma + g.v_begin,
+                               owned * 8ull, hipMemcpyDeviceToHost, s));
+    }
+    HIP_CHECK(hipStreamSynchronize(s));
+    res.i64.resize(owned);
+    for (uint32_t i = 0; i < owned; ++i)
+      res.i64[i] = d32[i] == 0xFFFFFFFFu
+                       ? std::numeric_limits<int64_t>::max()
+                       : static_cast<int64_t>(d32[i]);
+  }
+  return res;
 }
 
 }  // namespace grapehip

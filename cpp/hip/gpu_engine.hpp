@@ -104,7 +104,8 @@ struct DeviceGraph {
 
 struct GpuRunResult {
   std::vector<int64_t> i64;   // BFS depth / WCC & CDLP labels (owned range)
-  std::vector<double> f64;    // SSSP dist / PR rank / LCC coeff
+  std::vector<double> f64;    // SSSP dist / PR rank / LCC coeff / BC delta
+  std::vector<double> f64b;   // BC path counts (sigma); empty otherwise
   int rounds = 0;
   double seconds = 0;         // max over ranks, kernel-side barrier-bracketed
   uint64_t traversed_edges = 0;  // for TEPS accounting (global)
@@ -145,6 +146,9 @@ class GpuContext {
   GpuRunResult kcore(DeviceGraph& g, int k, bool fetch = true);
   // i64: coreness
   GpuRunResult core_decomposition(DeviceGraph& g, bool fetch = true);
+  // single-source Brandes on the stored out-CSR (cpp/apps/bc.hpp semantics)
+  // f64: dependency delta, f64b: path counts, i64: depth; rounds: levels
+  GpuRunResult bc(DeviceGraph& g, int64_t source, bool fetch = true);
 
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device

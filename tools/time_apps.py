@@ -10,6 +10,9 @@ ap.add_argument("--apps", default="bfs,sssp,pagerank,wcc,cdlp,lcc,kcore,"
                                   "core_decomposition")
 ap.add_argument("--cdlp-iters", type=int, default=10)
 ap.add_argument("--kcore-k", type=int, default=3)
+ap.add_argument("--repeat", type=int, default=1,
+                help="timed runs per app; above 1 every time is also "
+                     "listed under <app>_ms_all")
 ap.add_argument("--warmup", type=int, default=1,
                 help="untimed runs per app first (absorbs one-time costs "
                      "like hipGraph capture, matching bench.py)")
@@ -35,6 +38,8 @@ def run_app(app):
         return eng.kcore(g, args.kcore_k, values=False)
     if app == "core_decomposition":
         return eng.core_decomposition(g, values=False)
+    if app == "bc":  # not in the default list
+        return eng.bc(g, 0, values=False)
     raise SystemExit("unknown app " + app)
 
 
@@ -57,6 +62,11 @@ for app in args.apps.split(","):
         r = eng.lcc(g, values=False)
     else:
         r = run_app(app)
+    if args.repeat > 1:
+        times = [r["seconds"]]
+        for _ in range(args.repeat - 1):
+            times.append(run_app(app)["seconds"])
+        out[app + "_ms_all"] = [round(t * 1e3, 2) for t in times]
     out[app + "_ms"] = round(r["seconds"] * 1e3, 2)
     out[app + "_rounds"] = r["rounds"]
 print(json.dumps(out))

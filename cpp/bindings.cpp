@@ -377,6 +377,36 @@ PYBIND11_MODULE(_core, m) {
              throw std::runtime_error("no hip");
 #endif
            })
+      .def("_debug_sort_rows",
+           [](PyEngine& e, py::array_t<uint64_t, py::array::c_style |
+                                                     py::array::forcecast> off,
+              py::array_t<uint32_t, py::array::c_style |
+                                        py::array::forcecast> dst,
+              std::optional<py::array_t<float, py::array::c_style |
+                                                   py::array::forcecast>> w)
+               -> py::object {
+#ifdef GRAPEHIP_WITH_HIP
+             std::vector<uint64_t> h_off(off.data(), off.data() + off.size());
+             std::vector<uint32_t> h_dst(dst.data(), dst.data() + dst.size());
+             auto as_array = [](const auto& v) {
+               return py::array_t<typename std::decay_t<decltype(v)>::
+                                      value_type>(v.size(), v.data());
+             };
+             if (!w)
+               return as_array(
+                   e.gpu->debug_sort_rows(h_off, std::move(h_dst), nullptr));
+             std::vector<float> h_w(w->data(), w->data() + w->size());
+             auto out =
+                 e.gpu->debug_sort_rows(h_off, std::move(h_dst), &h_w);
+             return py::make_tuple(as_array(out), as_array(h_w));
+#else
+             (void)off;
+             (void)dst;
+             (void)w;
+             throw std::runtime_error("no hip");
+#endif
+           },
+           py::arg("off"), py::arg("dst"), py::arg("w") = py::none())
       .def("allreduce_max",
            [](PyEngine& e, double v) {
              py::gil_scoped_release rel;

@@ -442,24 +442,52 @@ __global__ void scatter_edges_kernel(const uint32_t* src, const uint32_t* dst,
 }
 
 // ===========================================================================
-// Segmented adjacency sort (ascending dst per CSR row). Applied once after
-// the device CSR is built: ascending neighbor ids turn the pull kernels'
-// random gathers into locally-increasing streams (L2-friendlier) and give
-// deterministic adjacency order. Weighted rows sort (dst,weight) pairs
-// packed into u64. LDS bitonic for rows <= 4096, pow2-padded global
-// scratch bitonic for heavier rows.
+// Segmented sort (ascending keys per CSR row), shared by the adjacency sort
+// of a freshly built device CSR and by LCC's oriented CSR. Ascending
+// neighbor ids turn the pull kernels' random gathers into locally-increasing
+// streams (L2-friendlier) and give deterministic adjacency order. A codec
+// loads the key of row position i and stores it back; the padding key sorts
+// last. LDS bitonic for rows <= kSegSortLds keys, pow2-padded global scratch
+// bitonic for heavier rows.
 // ===========================================================================
 
-constexpr uint32_t kSegSortLds = 4096;
+constexpr uint32_t kSegSortLds = 4096;  // 32 KB of LDS for u64, 16 KB for u32
 
-__device__ __forceinline__ void bitonic_stage_u64(unsigned long long* a,
-                                                  uint32_t n, uint32_t k,
-                                                  uint32_t j) {
+// (dst, optional weight) pairs packed into u64, dst in the high half
+struct PairKeyCodec {
+  using Key = unsigned long long;
+  static constexpr Key kPad = ~0ull;
+  uint32_t* __restrict__ dst;
+  float* __restrict__ w;  // null: unweighted
+  __device__ __forceinline__ Key load(uint64_t i) const {
+    return (static_cast<unsigned long long>(dst[i]) << 32) |
+           (w ? __float_as_uint(w[i]) : 0u);
+  }
+  __device__ __forceinline__ void store(uint64_t i, Key k) const {
+    dst[i] = static_cast<uint32_t>(k >> 32);
+    if (w) w[i] = __uint_as_float(static_cast<uint32_t>(k));
+  }
+};
+
+// plain u32 keys; vertex ids never reach the padding value
+struct U32KeyCodec {
+  using Key = uint32_t;
+  static constexpr Key kPad = 0xFFFFFFFFu;
+  uint32_t* __restrict__ dst;
+  __device__ __forceinline__ Key load(uint64_t i) const { return dst[i]; }
+  __device__ __forceinline__ void store(uint64_t i, Key k) const {
+    dst[i] = k;
+  }
+};
+
+template <typename Key>
+__device__ __forceinline__ void bitonic_stage(Key* a, uint32_t n, uint32_t k,
+                                              uint32_t j) {
   for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
     uint32_t ij = i ^ j;
     if (ij > i) {
       bool up = (i & k) == 0;
-      unsigned long long x = a[i], y = a[ij];
+      Key x = a[i], y = a[ij];
       if ((x > y) == up) {
         a[i] = y;
         a[ij] = x;
@@ -468,6 +496,9 @@ __device__ __forceinline__ void bitonic_stage_u64(unsigned long long* a,
   }
 }
 
+// bucket rows for the sort tiers by length (block-aggregated counter
+// reservation, same pattern as bucket_rows_kernel); rows of 0 or 1 keys
+// are in no bucket
 __global__ void seg_sortbucket_kernel(const uint64_t* __restrict__ off,
                                       uint32_t rows_n, uint32_t* lds_rows,
                                       unsigned long long* c_lds,
@@ -503,12 +534,13 @@ __global__ void seg_sortbucket_kernel(const uint64_t* __restrict__ off,
   }
 }
 
+template <typename Codec>
 __global__ void seg_sort_lds_kernel(const uint64_t* __restrict__ off,
-                                    uint32_t* __restrict__ dst,
-                                    float* __restrict__ w,
+                                    Codec c,
                                     const uint32_t* __restrict__ rows,
                                     uint64_t nrows) {
-  __shared__ unsigned long long s_a[kSegSortLds];
+  using Key = typename Codec::Key;
+  __shared__ Key s_a[kSegSortLds];
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
     uint64_t b = off[r];
@@ -516,20 +548,15 @@ __global__ void seg_sort_lds_kernel(const uint64_t* __restrict__ off,
     uint32_t cap = 2;
     while (cap < n) cap <<= 1;
     for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x)
-      s_a[k] = k < n
-                   ? ((static_cast<unsigned long long>(dst[b + k]) << 32) |
-                      (w ? __float_as_uint(w[b + k]) : 0u))
-                   : ~0ull;
+      s_a[k] = k < n ? c.load(b + k) : Codec::kPad;
     __syncthreads();
     for (uint32_t k = 2; k <= cap; k <<= 1)
       for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        bitonic_stage_u64(s_a, cap, k, j);
+        bitonic_stage(s_a, cap, k, j);
         __syncthreads();
       }
-    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) {
-      dst[b + k] = static_cast<uint32_t>(s_a[k] >> 32);
-      if (w) w[b + k] = __uint_as_float(static_cast<uint32_t>(s_a[k]));
-    }
+    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x)
+      c.store(b + k, s_a[k]);
     __syncthreads();
   }
 }
@@ -549,13 +576,12 @@ __global__ void seg_bigcap_kernel(const uint64_t* __restrict__ off,
   }
 }
 
-__global__ void seg_bigpad_kernel(const uint64_t* __restrict__ off,
-                                  const uint32_t* __restrict__ dst,
-                                  const float* __restrict__ w,
+template <typename Codec>
+__global__ void seg_bigpad_kernel(const uint64_t* __restrict__ off, Codec c,
                                   const uint32_t* __restrict__ rows,
                                   uint64_t nrows,
                                   const uint64_t* __restrict__ pad_off,
-                                  unsigned long long* __restrict__ scratch) {
+                                  typename Codec::Key* __restrict__ scratch) {
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
     uint64_t b = off[r];
@@ -563,46 +589,40 @@ __global__ void seg_bigpad_kernel(const uint64_t* __restrict__ off,
     uint64_t pb = pad_off[i];
     uint64_t cap = pad_off[i + 1] - pb;
     for (uint64_t k = threadIdx.x; k < cap; k += blockDim.x)
-      scratch[pb + k] =
-          k < n ? ((static_cast<unsigned long long>(dst[b + k]) << 32) |
-                   (w ? __float_as_uint(w[b + k]) : 0u))
-                : ~0ull;
+      scratch[pb + k] = k < n ? c.load(b + k) : Codec::kPad;
   }
 }
 
+template <typename Key>
 __global__ void seg_bigsort_kernel(const uint64_t* __restrict__ pad_off,
                                    uint64_t nrows,
-                                   unsigned long long* __restrict__ scratch) {
+                                   Key* __restrict__ scratch) {
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint64_t pb = pad_off[i];
     uint32_t cap = static_cast<uint32_t>(pad_off[i + 1] - pb);
-    unsigned long long* a = scratch + pb;
+    Key* a = scratch + pb;
     for (uint32_t k = 2; k <= cap; k <<= 1)
       for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        bitonic_stage_u64(a, cap, k, j);
+        bitonic_stage(a, cap, k, j);
         __syncthreads();
       }
   }
 }
 
-__global__ void seg_bigunpad_kernel(const uint64_t* __restrict__ off,
-                                    uint32_t* __restrict__ dst,
-                                    float* __restrict__ w,
+template <typename Codec>
+__global__ void seg_bigunpad_kernel(const uint64_t* __restrict__ off, Codec c,
                                     const uint32_t* __restrict__ rows,
                                     uint64_t nrows,
                                     const uint64_t* __restrict__ pad_off,
-                                    const unsigned long long* __restrict__
+                                    const typename Codec::Key* __restrict__
                                         scratch) {
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
     uint64_t b = off[r];
     uint64_t n = off[r + 1] - b;
     uint64_t pb = pad_off[i];
-    for (uint64_t k = threadIdx.x; k < n; k += blockDim.x) {
-      dst[b + k] = static_cast<uint32_t>(scratch[pb + k] >> 32);
-      if (w) w[b + k] = __uint_as_float(
-                 static_cast<uint32_t>(scratch[pb + k]));
-    }
+    for (uint64_t k = threadIdx.x; k < n; k += blockDim.x)
+      c.store(b + k, scratch[pb + k]);
   }
 }
 
@@ -2501,6 +2521,74 @@ double wall_s() {
       .count();
 }
 
+// The timed region of an app run. Opens with control-plane barrier, device
+// sync, clock; finish() closes with device sync, barrier, clock, and takes
+// the slowest rank's time. Whatever the app enqueues between the two is
+// what `seconds` measures.
+struct RunBracket {
+  GpuContext::Impl& I;
+  TcpComm* comm;
+  double t0;
+  uint64_t b_p2p0, b_coll0;
+  RunBracket(GpuContext::Impl& impl, TcpComm* c) : I(impl), comm(c) {
+    if (comm) comm->barrier();
+    HIP_CHECK(hipDeviceSynchronize());
+    t0 = wall_s();
+    b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  }
+  double elapsed_ms() const { return (wall_s() - t0) * 1e3; }
+  GpuRunResult finish(int rounds, uint64_t traversed_edges) const {
+    HIP_CHECK(hipDeviceSynchronize());
+    if (comm) comm->barrier();
+    double t1 = wall_s();
+    GpuRunResult res;
+    res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
+    res.bytes_coll = I.dc.bytes_coll - b_coll0;
+    res.rounds = rounds;
+    res.seconds = comm ? comm->allreduce_max_double(t1 - t0) : (t1 - t0);
+    res.traversed_edges = traversed_edges;
+    return res;
+  }
+};
+
+// Sorts the keys of every row of `off` (rows_n + 1 offsets into the codec's
+// arrays) ascending, on stream s. Reads the two tier counts back, so it
+// syncs s once; the sort kernels themselves are left in flight.
+template <typename Codec>
+void segmented_sort_rows(const uint64_t* off, uint32_t rows_n, Codec codec,
+                         hipStream_t s, ScanTemp& scan) {
+  using Key = typename Codec::Key;
+  DeviceBuffer<uint32_t> lds_rows(rows_n ? rows_n : 1),
+      big_rows(rows_n ? rows_n : 1);
+  DeviceBuffer<unsigned long long> cnts(2);
+  cnts.zero(s);
+  if (rows_n)
+    seg_sortbucket_kernel<<<grid_for(rows_n), kBlock, 0, s>>>(
+        off, rows_n, lds_rows.data(), cnts.data() + 0, big_rows.data(),
+        cnts.data() + 1);
+  auto h = cnts.download(s);
+  const uint64_t n_lds = h[0], n_big = h[1];
+  if (n_lds)
+    seg_sort_lds_kernel<<<std::min<uint64_t>(n_lds, kMaxGrid), kBlock, 0,
+                          s>>>(off, codec, lds_rows.data(), n_lds);
+  if (n_big) {
+    const int grid = static_cast<int>(std::min<uint64_t>(n_big, kMaxGrid));
+    DeviceBuffer<uint32_t> caps(n_big);
+    DeviceBuffer<uint64_t> pad_off(n_big + 1);
+    seg_bigcap_kernel<<<grid_for(n_big), kBlock, 0, s>>>(
+        off, big_rows.data(), n_big, caps.data());
+    uint64_t pad_total =
+        exclusive_scan(caps.data(), pad_off.data(), n_big, s, scan);
+    DeviceBuffer<Key> scratch(pad_total);
+    seg_bigpad_kernel<<<grid, kBlock, 0, s>>>(
+        off, codec, big_rows.data(), n_big, pad_off.data(), scratch.data());
+    seg_bigsort_kernel<<<grid, kBlock, 0, s>>>(pad_off.data(), n_big,
+                                               scratch.data());
+    seg_bigunpad_kernel<<<grid, kBlock, 0, s>>>(
+        off, codec, big_rows.data(), n_big, pad_off.data(), scratch.data());
+  }
+}
+
 }  // namespace
 
 DeviceGraph::~DeviceGraph() {
@@ -2579,6 +2667,45 @@ std::vector<uint64_t> GpuContext::debug_scan(const std::vector<uint32_t>& in) {
   return d_out.download(s);
 }
 
+std::vector<uint32_t> GpuContext::debug_sort_rows(
+    const std::vector<uint64_t>& off, std::vector<uint32_t> dst,
+    std::vector<float>* w) {
+  if (off.empty()) return dst;
+  if (off.back() > dst.size() || (w && w->size() != dst.size()))
+    throw std::runtime_error("debug_sort_rows: offsets do not match the keys");
+  if (!std::is_sorted(off.begin(), off.end()) || off.size() > 0xFFFFFFFFull)
+    throw std::runtime_error("debug_sort_rows: offsets must ascend");
+  hipStream_t s = impl_->compute;
+  const uint32_t rows_n = static_cast<uint32_t>(off.size() - 1);
+  DeviceBuffer<uint64_t> d_off;
+  d_off.upload(off, s);
+  DeviceBuffer<uint32_t> d_dst(dst.size() ? dst.size() : 1);
+  DeviceBuffer<float> d_w(w && dst.size() ? dst.size() : 1);
+  if (!dst.empty()) {
+    HIP_CHECK(hipMemcpyAsync(d_dst.data(), dst.data(), dst.size() * 4,
+                             hipMemcpyHostToDevice, s));
+    if (w)
+      HIP_CHECK(hipMemcpyAsync(d_w.data(), w->data(), dst.size() * 4,
+                               hipMemcpyHostToDevice, s));
+  }
+  if (w)
+    segmented_sort_rows(d_off.data(), rows_n,
+                        PairKeyCodec{d_dst.data(), d_w.data()}, s,
+                        impl_->scan);
+  else
+    segmented_sort_rows(d_off.data(), rows_n, U32KeyCodec{d_dst.data()}, s,
+                        impl_->scan);
+  if (!dst.empty()) {
+    HIP_CHECK(hipMemcpyAsync(dst.data(), d_dst.data(), dst.size() * 4,
+                             hipMemcpyDeviceToHost, s));
+    if (w)
+      HIP_CHECK(hipMemcpyAsync(w->data(), d_w.data(), dst.size() * 4,
+                               hipMemcpyDeviceToHost, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));
+  return dst;
+}
+
 // ---------------------------------------------------------------------------
 // Graph construction
 // ---------------------------------------------------------------------------
@@ -2621,36 +2748,9 @@ void sort_csr_rows(const DeviceBuffer<uint64_t>& off,
                    DeviceBuffer<uint32_t>& dst, DeviceBuffer<float>* w,
                    uint32_t rows_n, hipStream_t s, ScanTemp& scan) {
   if (rows_n == 0) return;
-  DeviceBuffer<uint32_t> lds_rows(rows_n), big_rows(rows_n);
-  DeviceBuffer<unsigned long long> cnts(2);
-  cnts.zero(s);
-  seg_sortbucket_kernel<<<grid_for(rows_n), kBlock, 0, s>>>(
-      off.data(), rows_n, lds_rows.data(), cnts.data() + 0, big_rows.data(),
-      cnts.data() + 1);
-  auto h = cnts.download(s);
-  if (h[0])
-    seg_sort_lds_kernel<<<std::min<uint64_t>(h[0], kMaxGrid), kBlock, 0,
-                          s>>>(off.data(), dst.data(),
-                               w ? w->data() : nullptr, lds_rows.data(),
-                               h[0]);
-  if (h[1]) {
-    DeviceBuffer<uint32_t> caps(h[1]);
-    DeviceBuffer<uint64_t> pad_off(h[1] + 1);
-    seg_bigcap_kernel<<<grid_for(h[1]), kBlock, 0, s>>>(
-        off.data(), big_rows.data(), h[1], caps.data());
-    uint64_t pad_total =
-        exclusive_scan(caps.data(), pad_off.data(), h[1], s, scan);
-    DeviceBuffer<unsigned long long> scratch(pad_total);
-    seg_bigpad_kernel<<<std::min<uint64_t>(h[1], kMaxGrid), kBlock, 0, s>>>(
-        off.data(), dst.data(), w ? w->data() : nullptr, big_rows.data(),
-        h[1], pad_off.data(), scratch.data());
-    seg_bigsort_kernel<<<std::min<uint64_t>(h[1], kMaxGrid), kBlock, 0,
-                         s>>>(pad_off.data(), h[1], scratch.data());
-    seg_bigunpad_kernel<<<std::min<uint64_t>(h[1], kMaxGrid), kBlock, 0,
-                          s>>>(off.data(), dst.data(),
-                               w ? w->data() : nullptr, big_rows.data(),
-                               h[1], pad_off.data(), scratch.data());
-  }
+  segmented_sort_rows(off.data(), rows_n,
+                      PairKeyCodec{dst.data(), w ? w->data() : nullptr}, s,
+                      scan);
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
@@ -2957,12 +3057,46 @@ std::unique_ptr<DeviceGraph> GpuContext::upload(const Fragment& frag) {
 namespace grapehip {
 
 // ---------------------------------------------------------------------------
-// Degree buckets over the pull CSR (undirected: out == neighborhood;
-// directed: in-CSR). Built once per graph, reused by PR pull + BFS pull.
+// Materialize a bitmap frontier into a queue; returns the count.
+// bm covers bits [0, nbits) (owned rows); q entries are global vids
+// (bit_base = v_begin). Clears the bitmap.
 // ---------------------------------------------------------------------------
 static uint64_t compact_frontier(GpuContext::Impl& I, uint32_t* bm_words,
                                  size_t nbits, uint32_t bit_base, uint32_t* q,
-                                 hipStream_t s);
+                                 hipStream_t s) {
+  size_t nwords = (nbits + 31) / 32;
+  if (I.frontier_deg.size() < nwords)
+    I.frontier_deg.resize(nwords + (nwords >> 2) + 64);
+  if (I.frontier_off.size() < nwords + 1)
+    I.frontier_off.resize(nwords + (nwords >> 2) + 65);
+  popc_words_kernel<<<grid_for(nwords), kBlock, 0, s>>>(bm_words, nwords,
+                                                        I.frontier_deg.data());
+  uint64_t total = exclusive_scan(I.frontier_deg.data(),
+                                  I.frontier_off.data(), nwords, s, I.scan);
+  if (total)
+    fill_frontier_kernel<<<grid_for(nwords), kBlock, 0, s>>>(
+        bm_words, nwords, I.frontier_off.data(), bit_base, q);
+  return total;
+}
+
+// compact_frontier for a frontier app: returns this rank's count and writes
+// the count over all ranks, which every rank needs to leave the loop in the
+// same round. One rank: no collective.
+static uint32_t compact_frontier_global(GpuContext::Impl& I, TcpComm* comm,
+                                        int world, uint32_t* bm_words,
+                                        size_t nbits, uint32_t bit_base,
+                                        uint32_t* q, hipStream_t s,
+                                        uint64_t& global) {
+  uint32_t qn = static_cast<uint32_t>(
+      compact_frontier(I, bm_words, nbits, bit_base, q, s));
+  global = world > 1 ? comm->allreduce_sum(qn) : qn;
+  return qn;
+}
+
+// ---------------------------------------------------------------------------
+// Degree buckets over the pull CSR (undirected: out == neighborhood;
+// directed: in-CSR). Built once per graph, reused by PR pull + BFS pull.
+// ---------------------------------------------------------------------------
 
 // Also builds rows_active and the hub work list (see DeviceGraph). All of
 // it hangs off the DeviceGraph and is built once: a mutated graph is
@@ -3115,29 +3249,6 @@ static void ensure_pr_tiles(DeviceGraph& g, GpuContext::Impl& I,
 }
 
 // ---------------------------------------------------------------------------
-// Materialize a bitmap frontier into a queue; returns the count.
-// bm covers bits [0, nbits) (owned rows); q entries are global vids
-// (bit_base = v_begin). Clears the bitmap.
-// ---------------------------------------------------------------------------
-static uint64_t compact_frontier(GpuContext::Impl& I, uint32_t* bm_words,
-                                 size_t nbits, uint32_t bit_base, uint32_t* q,
-                                 hipStream_t s) {
-  size_t nwords = (nbits + 31) / 32;
-  if (I.frontier_deg.size() < nwords)
-    I.frontier_deg.resize(nwords + (nwords >> 2) + 64);
-  if (I.frontier_off.size() < nwords + 1)
-    I.frontier_off.resize(nwords + (nwords >> 2) + 65);
-  popc_words_kernel<<<grid_for(nwords), kBlock, 0, s>>>(bm_words, nwords,
-                                                        I.frontier_deg.data());
-  uint64_t total = exclusive_scan(I.frontier_deg.data(),
-                                  I.frontier_off.data(), nwords, s, I.scan);
-  if (total)
-    fill_frontier_kernel<<<grid_for(nwords), kBlock, 0, s>>>(
-        bm_words, nwords, I.frontier_off.data(), bit_base, q);
-  return total;
-}
-
-// ---------------------------------------------------------------------------
 // Halo host-side flush: pack per-peer pairs, exchange counts over TCP,
 // ncclSend/Recv payloads over xGMI. Returns #received pairs (in recvbuf).
 // TAKE packs with halo_pack_take_kernel: the packed state entries are zero
@@ -3198,6 +3309,39 @@ uint64_t halo_flush(GpuContext::Impl& I, TcpComm* comm, int rank, int world,
   I.ev_comm.wait_on(s);
   // self pairs (should be none — owned handled locally)
   return recv_total;
+}
+
+// Sizes the halo scratch for `cap` indices per peer and a dedup bitmap of
+// bm_words, and returns the device handle the push functors carry. A single
+// rank sizes nothing: its handle holds whatever the buffers hold and is
+// never dereferenced.
+static DevHalo halo_reserve(GpuContext::Impl& I, int world, uint64_t cap,
+                            uint32_t slice, uint64_t bm_words) {
+  if (world > 1) {
+    I.halo_idx.resize(static_cast<uint64_t>(world) * cap);
+    I.halo_cnt.resize(world);
+    I.halo_bm.resize(bm_words);
+  }
+  return DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
+                 DevBitmap{I.halo_bm.data()}, cap, slice, world};
+}
+
+// Empties the halo scratch (multi-rank callers only).
+static void halo_reset(GpuContext::Impl& I, hipStream_t s) {
+  I.halo_cnt.zero(s);
+  I.halo_bm.zero(s);
+}
+
+// One halo round: flush this rank's pairs to their owners, then apply the
+// received pairs with recv_op (multi-rank callers only).
+template <typename T, bool TAKE = false, typename RecvOp>
+void halo_round(GpuContext::Impl& I, TcpComm* comm, int rank, int world,
+                std::conditional_t<TAKE, T*, const T*> state, uint64_t cap,
+                RecvOp recv_op, hipStream_t s) {
+  uint64_t nrecv = halo_flush<T, TAKE>(I, comm, rank, world, state, cap, s);
+  if (nrecv)
+    halo_process_kernel<T, RecvOp><<<grid_for(nrecv), kBlock, 0, s>>>(
+        reinterpret_cast<HaloPair<T>*>(I.recvbuf.data()), nrecv, recv_op);
 }
 
 // ===========================================================================
@@ -3569,19 +3713,48 @@ void launch_expand(GpuContext::Impl& I, const DevGraphView& view,
   }
 }
 
+// Degree prefix of a frontier into foff (qn + 1 entries), through fdeg;
+// returns the frontier's arc total. Grows the two buffers as needed; an
+// empty frontier launches nothing and leaves them alone.
+static uint64_t scan_frontier_degrees(GpuContext::Impl& I,
+                                      const DevGraphView& view,
+                                      const uint32_t* q, uint32_t qn,
+                                      DeviceBuffer<uint32_t>& fdeg,
+                                      DeviceBuffer<uint64_t>& foff,
+                                      hipStream_t s) {
+  if (qn == 0) return 0;
+  if (fdeg.size() < qn) fdeg.resize(qn + (qn >> 2) + 64);
+  if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
+  gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
+                                                    fdeg.data());
+  return exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
+}
+
 // generic frontier expansion helper: scan degrees, then launch_expand
 template <typename Op>
 void expand_frontier(GpuContext::Impl& I, const DevGraphView& view,
                      const uint32_t* q, uint32_t qn, Op op, hipStream_t s) {
   if (qn == 0) return;
-  if (I.frontier_deg.size() < qn) I.frontier_deg.resize(qn + (qn >> 2) + 64);
-  if (I.frontier_off.size() < qn + 1)
-    I.frontier_off.resize(qn + (qn >> 2) + 65);
-  gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
-                                                    I.frontier_deg.data());
-  uint64_t total = exclusive_scan(I.frontier_deg.data(),
-                                  I.frontier_off.data(), qn, s, I.scan);
+  uint64_t total = scan_frontier_degrees(I, view, q, qn, I.frontier_deg,
+                                         I.frontier_off, s);
   launch_expand(I, view, q, qn, I.frontier_off.data(), total, op, s);
+}
+
+// owned slice of a u32 depth array as int64, unreached = INT64_MAX
+static std::vector<int64_t> fetch_depth_i64(const uint32_t* depth,
+                                            const DeviceGraph& g,
+                                            hipStream_t s) {
+  const uint32_t owned = g.owned();
+  std::vector<uint32_t> d32(owned);
+  if (owned)
+    HIP_CHECK(hipMemcpyAsync(d32.data(), depth + g.v_begin, owned * 4ull,
+                             hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  std::vector<int64_t> out(owned);
+  for (uint32_t i = 0; i < owned; ++i)
+    out[i] = d32[i] == 0xFFFFFFFFu ? std::numeric_limits<int64_t>::max()
+                                   : static_cast<int64_t>(d32[i]);
+  return out;
 }
 
 // ---------------------------------------------------------------------------
@@ -3615,32 +3788,22 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
   uint32_t* const next_bm = I.trav_near_bm.data();
   DeviceBuffer<uint32_t>& fdeg = I.trav_fdeg;
   DeviceBuffer<uint64_t>& foff = I.trav_foff;
-  if (multi) {
-    I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
-    I.halo_cnt.resize(world_);
-    I.halo_bm.resize((static_cast<uint64_t>(nv_pad) + 31) / 32);
-  }
+  const DevHalo halo = halo_reserve(
+      I, world_, cap, view.slice, (static_cast<uint64_t>(nv_pad) + 31) / 32);
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   if (nv_pad)
     HIP_CHECK(hipMemsetAsync(depth, 0xFF, static_cast<size_t>(nv_pad) * 4, s));
   HIP_CHECK(hipMemsetAsync(next_bm, 0, bm_words * 4, s));
-  if (multi) {
-    I.halo_cnt.zero(s);
-    I.halo_bm.zero(s);
-  }
+  if (multi) halo_reset(I, s);
   uint32_t src = map_source(g, source, s);
   if (src >= g.v_begin && src < g.v_end)
     bfs_seed_kernel<<<1, 1, 0, s>>>(depth, src, g.v_begin,
                                     next_bm);
-  uint32_t qn =
-      static_cast<uint32_t>(compact_frontier(I, next_bm, owned,
-                                             g.v_begin, q, s));
-  uint64_t global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+  uint64_t global_curr = 0;
+  uint32_t qn = compact_frontier_global(I, comm_, world_, next_bm, owned,
+                                        g.v_begin, q, s, global_curr);
   uint32_t level = 0;
   int rounds = 0;
   // Beamer-style switch: pull when the frontier's out-edges exceed a
@@ -3652,14 +3815,7 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
   const uint64_t pull_edge_threshold = g.total_edges / pull_div;
   while (global_curr > 0) {
     bool use_pull = false;
-    uint64_t fedges = 0;
-    if (qn) {
-      if (fdeg.size() < qn) fdeg.resize(qn + (qn >> 2) + 64);
-      if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
-      gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
-                                                        fdeg.data());
-      fedges = exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
-    }
+    uint64_t fedges = scan_frontier_degrees(I, view, q, qn, fdeg, foff, s);
     if (pull_capable) {
       uint64_t gedges = multi ? comm_->allreduce_sum(fedges) : fedges;
       use_pull = gedges > pull_edge_threshold;
@@ -3689,53 +3845,24 @@ GpuRunResult GpuContext::bfs(DeviceGraph& g, int64_t source,
             depth, level, nb);
     } else {
       BfsOp op{depth, level + 1, DevBitmap{next_bm}, g.v_begin,
-               g.v_end, multi,
-               DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
-                       DevBitmap{I.halo_bm.data()}, cap, view.slice, world_}};
+               g.v_end, multi, halo};
       launch_expand(I, view, q, qn, foff.data(), fedges, op, s);
-      if (multi) {
-        uint64_t nrecv = halo_flush<uint32_t>(I, comm_, rank_, world_,
-                                              depth, cap, s);
-        if (nrecv)
-          halo_process_kernel<uint32_t, BfsRecvOp>
-              <<<grid_for(nrecv), kBlock, 0, s>>>(
-                  reinterpret_cast<HaloPair<uint32_t>*>(I.recvbuf.data()),
-                  nrecv,
-                  BfsRecvOp{depth, DevBitmap{next_bm},
-                            g.v_begin});
-      }
+      if (multi)
+        halo_round<uint32_t>(I, comm_, rank_, world_, depth, cap,
+                             BfsRecvOp{depth, DevBitmap{next_bm}, g.v_begin},
+                             s);
     }
-    qn = static_cast<uint32_t>(compact_frontier(I, next_bm, owned,
-                                                g.v_begin, q, s));
-    global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+    qn = compact_frontier_global(I, comm_, world_, next_bm, owned, g.v_begin,
+                                 q, s, global_curr);
     if (getenv("GRAPEHIP_DEBUG"))
       fprintf(stderr, "[bfs] level=%u mode=%s fedges=%lu next=%u t=%.1fms\n",
               level, use_pull ? "pull" : "push", (unsigned long)fedges, qn,
-              (wall_s() - t0) * 1e3);
+              br.elapsed_ms());
     ++level;
     ++rounds;
   }
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = rounds;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = g.input_edges;
-  if (fetch) {
-    std::vector<uint32_t> d32(owned);
-    HIP_CHECK(hipMemcpyAsync(d32.data(), depth + g.v_begin, owned * 4,
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    res.i64.resize(owned);
-    for (uint32_t i = 0; i < owned; ++i)
-      res.i64[i] = d32[i] == 0xFFFFFFFFu
-                       ? std::numeric_limits<int64_t>::max()
-                       : static_cast<int64_t>(d32[i]);
-  }
+  GpuRunResult res = br.finish(rounds, g.input_edges);
+  if (fetch) res.i64 = fetch_depth_i64(depth, g, s);
   return res;
 }
 
@@ -3769,11 +3896,7 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
   uint32_t* const far_bm = I.trav_far_bm.data();
   DeviceBuffer<uint32_t>& fdeg = I.trav_fdeg;
   DeviceBuffer<uint64_t>& foff = I.trav_foff;
-  if (multi) {
-    I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
-    I.halo_cnt.resize(world_);
-    I.halo_bm.resize(glob_words);
-  }
+  const DevHalo halo = halo_reserve(I, world_, cap, view.slice, glob_words);
   if (delta <= 0) {
     // sweep across LiveJournal/orkut/datagen shapes put the optimum on a
     // wide plateau around 16x the mean edge weight (profiles/ r01 sweep);
@@ -3794,19 +3917,13 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
     delta = static_cast<float>(16.0 * mean_w);
   }
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   fill(dist, std::numeric_limits<float>::max(), nv_pad, s);
   HIP_CHECK(hipMemsetAsync(fcnt, 0, 2 * sizeof(unsigned long long), s));
   HIP_CHECK(hipMemsetAsync(near_bm, 0, own_words * 4, s));
   if (glob_words) HIP_CHECK(hipMemsetAsync(far_bm, 0, glob_words * 4, s));
-  if (multi) {
-    I.halo_cnt.zero(s);
-    I.halo_bm.zero(s);
-  }
+  if (multi) halo_reset(I, s);
   uint32_t src = map_source(g, source, s);
   if (src >= g.v_begin && src < g.v_end)
     sssp_seed_kernel<<<1, 1, 0, s>>>(dist, src, g.v_begin,
@@ -3818,46 +3935,35 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
   int rounds = 0;
   unsigned long long zero = 0;
   std::vector<unsigned long long> hfc(2);
-  uint32_t qn = static_cast<uint32_t>(compact_frontier(
-      I, near_bm, owned, g.v_begin, nearq[ncur], s));
-  uint64_t g_near = multi ? comm_->allreduce_sum(qn) : qn;
+  uint64_t g_near = 0;
+  uint32_t qn = compact_frontier_global(I, comm_, world_, near_bm, owned,
+                                        g.v_begin, nearq[ncur], s, g_near);
   for (;;) {
     float prio_hi = prio + delta;
     uint64_t fedges = 0;
     if (qn) {
-      if (fdeg.size() < qn) fdeg.resize(qn + (qn >> 2) + 64);
-      if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
-      gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, nearq[ncur], qn,
-                                                        fdeg.data());
-      fedges = exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
+      fedges =
+          scan_frontier_degrees(I, view, nearq[ncur], qn, fdeg, foff, s);
       SsspOp op{dist, prio_hi, DevBitmap{near_bm},
                 DevQueue{farq[fcur], fcnt + fcur},
-                DevBitmap{far_bm}, g.v_begin, g.v_end, multi,
-                DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
-                        DevBitmap{I.halo_bm.data()}, cap, view.slice,
-                        world_}};
+                DevBitmap{far_bm}, g.v_begin, g.v_end, multi, halo};
       launch_expand(I, view, nearq[ncur], qn, foff.data(), fedges, op, s);
     }
-    if (multi) {
-      uint64_t nrecv =
-          halo_flush<float>(I, comm_, rank_, world_, dist, cap, s);
-      if (nrecv)
-        halo_process_kernel<float, SsspRecvOp>
-            <<<grid_for(nrecv), kBlock, 0, s>>>(
-                reinterpret_cast<HaloPair<float>*>(I.recvbuf.data()), nrecv,
-                SsspRecvOp{dist, prio_hi, DevBitmap{near_bm},
-                           DevQueue{farq[fcur], fcnt + fcur},
-                           DevBitmap{far_bm}, g.v_begin});
-    }
+    if (multi)
+      halo_round<float>(I, comm_, rank_, world_, dist, cap,
+                        SsspRecvOp{dist, prio_hi, DevBitmap{near_bm},
+                                   DevQueue{farq[fcur], fcnt + fcur},
+                                   DevBitmap{far_bm}, g.v_begin},
+                        s);
     ++rounds;
-    uint32_t next_qn = static_cast<uint32_t>(compact_frontier(
-        I, near_bm, owned, g.v_begin, nearq[1 - ncur], s));
-    g_near = multi ? comm_->allreduce_sum(next_qn) : next_qn;
+    uint32_t next_qn =
+        compact_frontier_global(I, comm_, world_, near_bm, owned, g.v_begin,
+                                nearq[1 - ncur], s, g_near);
     if (getenv("GRAPEHIP_DEBUG"))
       fprintf(stderr,
               "[sssp] round=%d prio=%.0f in=%u fedges=%lu next=%u t=%.1fms\n",
               rounds, prio, qn, (unsigned long)fedges, next_qn,
-              (wall_s() - t0) * 1e3);
+              br.elapsed_ms());
     ncur = 1 - ncur;
     qn = next_qn;
     if (g_near > 0) continue;
@@ -3879,9 +3985,8 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
             DevBitmap{far_bm});
       HIP_CHECK(hipMemcpyAsync(fcnt + fcur, &zero, 8,
                                hipMemcpyHostToDevice, s));
-      qn = static_cast<uint32_t>(compact_frontier(
-          I, near_bm, owned, g.v_begin, nearq[ncur], s));
-      g_near = multi ? comm_->allreduce_sum(qn) : qn;
+      qn = compact_frontier_global(I, comm_, world_, near_bm, owned,
+                                   g.v_begin, nearq[ncur], s, g_near);
       HIP_CHECK(hipMemcpyAsync(hfc.data(), fcnt, 16,
                                hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
@@ -3891,16 +3996,7 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
     }
     if (g_near == 0 && g_far == 0) break;
   }
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = rounds;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = g.input_edges;
+  GpuRunResult res = br.finish(rounds, g.input_edges);
   if (fetch) {
     std::vector<float> d32(owned);
     HIP_CHECK(hipMemcpyAsync(d32.data(), dist + g.v_begin, owned * 4,
@@ -3971,10 +4067,7 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
   DeviceBuffer<double> d_l1(tol > 0 ? 1 : 0);
   DevGraphView view = make_view(g, rank_, world_);
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   fill(rank_arr.data(), 1.0 / N, nv_pad, s);
   // Rows without a pull edge are in no bucket, so the row pulls never write
@@ -4198,16 +4291,8 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
     pr_fill_isolated_kernel<<<grid_for(owned), kBlock, 0, s>>>(
         pull_off, g.oe_off.data(), owned, g.v_begin, d_dangling.data() + 2,
         rank_arr.data());
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = rounds;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = static_cast<uint64_t>(iters) * g.total_edges;
+  GpuRunResult res =
+      br.finish(rounds, static_cast<uint64_t>(iters) * g.total_edges);
   if (fetch) {
     res.f64.resize(owned);
     HIP_CHECK(hipMemcpyAsync(res.f64.data(), rank_arr.data() + g.v_begin,
@@ -4249,10 +4334,7 @@ GpuRunResult GpuContext::wcc(DeviceGraph& g, bool fetch) {
   DeviceBuffer<uint32_t> chg_q;
   DeviceBuffer<uint32_t> pairs_all;
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   iota_kernel<<<grid_for(nv_pad), kBlock, 0, s>>>(parent.data(), 0, nv_pad);
   if (multi) chg_bm.zero(s);
@@ -4416,16 +4498,7 @@ GpuRunResult GpuContext::wcc(DeviceGraph& g, bool fetch) {
       fprintf(stderr, "[wcc] output fixpoint passes=%d rounds=%d\n", passes,
               rounds);
   }
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = rounds;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = g.input_edges;
+  GpuRunResult res = br.finish(rounds, g.input_edges);
   if (fetch) {
     std::vector<uint32_t> lab(owned);
     const uint32_t* lab_src = parent.data() + g.v_begin;
@@ -5025,14 +5098,10 @@ GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
   DeviceBuffer<uint32_t> changed_q(owned ? owned : 1);
   DeviceBuffer<unsigned long long> d_nch(1);
   uint64_t halo_cap = nv_pad / (world_ ? world_ : 1);
-  if (multi) {
-    I.halo_idx.resize(static_cast<uint64_t>(world_) * halo_cap);
-    I.halo_cnt.resize(world_);
-    I.halo_bm.resize(dirty_words);
-    I.halo_cnt.zero(s);
-    I.halo_bm.zero(s);
-  }
   DevGraphView view = make_view(g, rank_, world_);
+  const DevHalo halo =
+      halo_reserve(I, world_, halo_cap, view.slice, dirty_words);
+  if (multi) halo_reset(I, s);
   DevGraphView view_in = view;
   if (g.directed) {
     view_in.oe_off = g.ie_off.data();
@@ -5041,10 +5110,7 @@ GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
   }
   if (multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   // label space must compare in OID order (reference tie-break): dense
   // renumber uses the sorted-oid table, hub renumber the inverse perm
@@ -5132,38 +5198,20 @@ GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
                                    changed_q.data(), s);
     if (qn) {
       CdlpDirtyOp op{DevBitmap{dirty.data()}, g.v_begin, g.v_end, multi,
-                     DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
-                             DevBitmap{I.halo_bm.data()}, halo_cap,
-                             view.slice, world_}};
+                     halo};
       expand_frontier(I, view, changed_q.data(),
                       static_cast<uint32_t>(qn), op, s);
       if (g.directed)
         expand_frontier(I, view_in, changed_q.data(),
                         static_cast<uint32_t>(qn), op, s);
     }
-    if (multi) {
-      uint64_t nrecv = halo_flush<uint32_t>(I, comm_, rank_, world_,
-                                            lab.data(), halo_cap, s);
-      if (nrecv) {
-        DevBitmap db{dirty.data()};
-        halo_process_kernel<uint32_t, CdlpMarkOp>
-            <<<grid_for(nrecv), kBlock, 0, s>>>(
-                reinterpret_cast<HaloPair<uint32_t>*>(I.recvbuf.data()),
-                nrecv, CdlpMarkOp{db});
-      }
-    }
+    if (multi)
+      halo_round<uint32_t>(I, comm_, rank_, world_, lab.data(), halo_cap,
+                           CdlpMarkOp{DevBitmap{dirty.data()}}, s);
   }
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = rounds;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges =
-      static_cast<uint64_t>(iters) * g.total_edges * (g.directed ? 2 : 1);
+  GpuRunResult res = br.finish(
+      rounds,
+      static_cast<uint64_t>(iters) * g.total_edges * (g.directed ? 2 : 1));
   if (fetch) {
     std::vector<uint32_t> l32(owned);
     HIP_CHECK(hipMemcpyAsync(l32.data(), lab.data() + g.v_begin, owned * 4,
@@ -5195,7 +5243,6 @@ GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
 // ---------------------------------------------------------------------------
 
 constexpr uint32_t kLccLdsSlots = 8192;  // 32 KB label-only LDS hash
-constexpr uint32_t kLccSortLds = 4096;   // 16 KB LDS bitonic bound
 
 // orientation: keep u in O(v) iff (D[u],u) > (D[v],v)
 __device__ __forceinline__ bool lcc_keep(uint32_t du, uint32_t u, uint32_t dv,
@@ -5615,151 +5662,6 @@ __global__ void lcc_compact_kernel(const uint64_t* __restrict__ ooff,
     uint64_t src = ooff[i];
     uint64_t dstb = goff[v_begin + i];
     for (uint32_t k = lane; k < n; k += kWave) gdst[dstb + k] = oadj[src + k];
-  }
-}
-
-// bucket rows for the sort tiers by oriented count (block-aggregated
-// counter reservation, same pattern as bucket_rows_kernel)
-__global__ void lcc_sortbucket_kernel(const uint64_t* __restrict__ goff,
-                                      uint32_t owned, uint32_t v_begin,
-                                      uint32_t* lds_rows,
-                                      unsigned long long* c_lds,
-                                      uint32_t* big_rows,
-                                      unsigned long long* c_big) {
-  __shared__ uint32_t s_cnt[2];
-  __shared__ unsigned long long s_base[2];
-  uint32_t* lists[2] = {lds_rows, big_rows};
-  unsigned long long* gcnt[2] = {c_lds, c_big};
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < owned;
-       base += stride) {
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t r = base + threadIdx.x;
-    int b = -1;
-    uint32_t loc = 0;
-    if (r < owned) {
-      uint64_t n = goff[v_begin + r + 1] - goff[v_begin + r];
-      if (n >= 2) {
-        b = n <= kLccSortLds ? 0 : 1;
-        loc = atomicAdd(&s_cnt[b], 1u);
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x])
-      s_base[threadIdx.x] =
-          atomicAdd(gcnt[threadIdx.x],
-                    static_cast<unsigned long long>(s_cnt[threadIdx.x]));
-    __syncthreads();
-    if (b >= 0) lists[b][s_base[b] + loc] = r;
-    __syncthreads();
-  }
-}
-
-__device__ __forceinline__ void bitonic_stage(uint32_t* a, uint32_t n,
-                                              uint32_t k, uint32_t j) {
-  for (uint32_t i = threadIdx.x; i < n; i += blockDim.x) {
-    uint32_t ij = i ^ j;
-    if (ij > i) {
-      bool up = (i & k) == 0;
-      uint32_t x = a[i], y = a[ij];
-      if ((x > y) == up) {
-        a[i] = y;
-        a[ij] = x;
-      }
-    }
-  }
-}
-
-// LDS bitonic over rows with count <= kLccSortLds (pad with 0xFFFFFFFF)
-__global__ void lcc_sort_lds_kernel(const uint64_t* __restrict__ goff,
-                                    const uint32_t* __restrict__ rows,
-                                    uint64_t nrows, uint32_t v_begin,
-                                    uint32_t* __restrict__ gdst) {
-  __shared__ uint32_t s_a[kLccSortLds];
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
-    uint32_t r = rows[i];
-    uint64_t b = goff[v_begin + r];
-    uint32_t n = static_cast<uint32_t>(goff[v_begin + r + 1] - b);
-    uint32_t cap = 2;
-    while (cap < n) cap <<= 1;
-    for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x)
-      s_a[k] = k < n ? gdst[b + k] : 0xFFFFFFFFu;
-    __syncthreads();
-    for (uint32_t k = 2; k <= cap; k <<= 1)
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        bitonic_stage(s_a, cap, k, j);
-        __syncthreads();
-      }
-    for (uint32_t k = threadIdx.x; k < n; k += blockDim.x) gdst[b + k] = s_a[k];
-    __syncthreads();
-  }
-}
-
-// global-scratch bitonic for heavy rows (pow2-padded pool)
-__global__ void lcc_bigpad_kernel(const uint64_t* __restrict__ goff,
-                                  const uint32_t* __restrict__ rows,
-                                  uint64_t nrows,
-                                  const uint64_t* __restrict__ pad_off,
-                                  const uint32_t* __restrict__ gdst,
-                                  uint32_t v_begin,
-                                  uint32_t* __restrict__ scratch) {
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
-    uint32_t r = rows[i];
-    uint64_t b = goff[v_begin + r];
-    uint64_t n = goff[v_begin + r + 1] - b;
-    uint64_t pb = pad_off[i];
-    uint64_t cap = pad_off[i + 1] - pb;
-    for (uint64_t k = threadIdx.x; k < cap; k += blockDim.x)
-      scratch[pb + k] = k < n ? gdst[b + k] : 0xFFFFFFFFu;
-  }
-}
-
-__global__ void lcc_sort_big_kernel(const uint64_t* __restrict__ pad_off,
-                                    uint64_t nrows,
-                                    uint32_t* __restrict__ scratch) {
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
-    uint64_t pb = pad_off[i];
-    uint32_t cap = static_cast<uint32_t>(pad_off[i + 1] - pb);
-    uint32_t* a = scratch + pb;
-    for (uint32_t k = 2; k <= cap; k <<= 1)
-      for (uint32_t j = k >> 1; j > 0; j >>= 1) {
-        bitonic_stage(a, cap, k, j);
-        __syncthreads();
-      }
-  }
-}
-
-__global__ void lcc_bigunpad_kernel(const uint64_t* __restrict__ goff,
-                                    const uint32_t* __restrict__ rows,
-                                    uint64_t nrows,
-                                    const uint64_t* __restrict__ pad_off,
-                                    const uint32_t* __restrict__ scratch,
-                                    uint32_t v_begin,
-                                    uint32_t* __restrict__ gdst) {
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
-    uint32_t r = rows[i];
-    uint64_t b = goff[v_begin + r];
-    uint64_t n = goff[v_begin + r + 1] - b;
-    uint64_t pb = pad_off[i];
-    for (uint64_t k = threadIdx.x; k < n; k += blockDim.x)
-      gdst[b + k] = scratch[pb + k];
-  }
-}
-
-__global__ void lcc_bigcap_kernel(const uint64_t* __restrict__ goff,
-                                  const uint32_t* __restrict__ rows,
-                                  uint64_t nrows, uint32_t v_begin,
-                                  uint32_t* __restrict__ caps) {
-  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
-                    threadIdx.x;
-       i < nrows; i += stride) {
-    uint32_t r = rows[i];
-    uint64_t n = goff[v_begin + r + 1] - goff[v_begin + r];
-    uint64_t cap = 2;
-    while (cap < n) cap <<= 1;
-    caps[i] = static_cast<uint32_t>(cap);
   }
 }
 
@@ -6542,10 +6444,7 @@ GpuRunResult GpuContext::lcc_directed(DeviceGraph& g, bool fetch) {
   std::vector<uint64_t> roff, soff;
   if (multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   DeviceBuffer<uint32_t> Dv(nv_pad);
   Dv.zero(s);
@@ -6757,16 +6656,7 @@ GpuRunResult GpuContext::lcc_directed(DeviceGraph& g, bool fetch) {
   if (owned)
     lcc_dir_finalize_kernel<<<grid_for(owned), kBlock, 0, s>>>(
         Tcnt.data(), Dv.data(), owned, g.v_begin, lcc_out.data());
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = 1;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = g.input_edges;
+  GpuRunResult res = br.finish(1, g.input_edges);
   if (fetch) {
     res.f64.resize(owned);
     HIP_CHECK(hipMemcpyAsync(res.f64.data(), lcc_out.data(), owned * 8,
@@ -6808,10 +6698,7 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
   DeviceBuffer<uint8_t> rstage_s, rstage_r;
   if (multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   // tier rows by combined degree (reuses the CDLP bucketer)
   DeviceBuffer<uint32_t> t_small(owned), t_mid(owned), t_large(owned);
@@ -6945,37 +6832,9 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
                                            g.v_begin, gdst.data());
     oadj.free();
 
-    // per-row ascending sort
-    DeviceBuffer<uint32_t> lds_rows(owned ? owned : 1),
-        big_rows(owned ? owned : 1);
-    DeviceBuffer<unsigned long long> scnt(2);
-    scnt.zero(s);
-    if (owned)
-      lcc_sortbucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-          goff.data(), owned, g.v_begin, lds_rows.data(), scnt.data() + 0,
-          big_rows.data(), scnt.data() + 1);
-    auto hs = scnt.download(s);
-    uint64_t n_lds = hs[0], n_big = hs[1];
-    if (n_lds)
-      lcc_sort_lds_kernel<<<std::min<int>(n_lds, kMaxGrid), kBlock, 0, s>>>(
-          goff.data(), lds_rows.data(), n_lds, g.v_begin, gdst.data());
-    if (n_big) {
-      DeviceBuffer<uint32_t> caps(n_big);
-      DeviceBuffer<uint64_t> pad_off(n_big + 1);
-      lcc_bigcap_kernel<<<grid_for(n_big), kBlock, 0, s>>>(
-          goff.data(), big_rows.data(), n_big, g.v_begin, caps.data());
-      uint64_t pad_total =
-          exclusive_scan(caps.data(), pad_off.data(), n_big, s, I.scan);
-      DeviceBuffer<uint32_t> scratch(pad_total);
-      lcc_bigpad_kernel<<<std::min<int>(n_big, kMaxGrid), kBlock, 0, s>>>(
-          goff.data(), big_rows.data(), n_big, pad_off.data(), gdst.data(),
-          g.v_begin, scratch.data());
-      lcc_sort_big_kernel<<<std::min<int>(n_big, kMaxGrid), kBlock, 0, s>>>(
-          pad_off.data(), n_big, scratch.data());
-      lcc_bigunpad_kernel<<<std::min<int>(n_big, kMaxGrid), kBlock, 0, s>>>(
-          goff.data(), big_rows.data(), n_big, pad_off.data(),
-          scratch.data(), g.v_begin, gdst.data());
-    }
+    // per-row ascending sort of the owned rows
+    segmented_sort_rows(goff.data() + g.v_begin, owned,
+                        U32KeyCodec{gdst.data()}, s, I.scan);
 
     // fetch the referenced remote rows (sorted by their owners above):
     // each owner packs exactly the rows each peer requested; payloads
@@ -7098,16 +6957,7 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
   if (owned)
     lcc_finalize_kernel<<<grid_for(owned), kBlock, 0, s>>>(
         Tcnt.data(), Dv.data(), owned, g.v_begin, lcc_out.data());
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = 1;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = g.input_edges;
+  GpuRunResult res = br.finish(1, g.input_edges);
   if (fetch) {
     res.f64.resize(owned);
     HIP_CHECK(hipMemcpyAsync(res.f64.data(), lcc_out.data(), owned * 8,
@@ -7159,16 +7009,10 @@ GpuRunResult GpuContext::peel(DeviceGraph& g, bool all_levels, int k,
   size_t bm_words = (static_cast<size_t>(owned) + 31) / 32 + 1;
   DeviceBuffer<uint32_t> next_bm(bm_words);
   DeviceBuffer<uint32_t> dec(multi ? nv_pad : 1);
-  if (multi) {
-    I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
-    I.halo_cnt.resize(world_);
-    I.halo_bm.resize((static_cast<uint64_t>(nv_pad) + 31) / 32);
-  }
+  const DevHalo halo = halo_reserve(
+      I, world_, cap, view.slice, (static_cast<uint64_t>(nv_pad) + 31) / 32);
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   int rounds = 0;
   core.fill_bytes(0xFF, s);  // -1: not peeled
@@ -7179,8 +7023,7 @@ GpuRunResult GpuContext::peel(DeviceGraph& g, bool all_levels, int k,
     scal.zero(s);
     if (multi) {
       dec.zero(s);
-      I.halo_cnt.zero(s);
-      I.halo_bm.zero(s);
+      halo_reset(I, s);
     }
     kcore_init_deg_kernel<<<grid_for(owned), kBlock, 0, s>>>(
         g.oe_off.data(), owned, deg.data(), scal.data() + 1);
@@ -7220,9 +7063,10 @@ GpuRunResult GpuContext::peel(DeviceGraph& g, bool all_levels, int k,
     }
     kcore_seed_kernel<<<grid_for(rows), kBlock, 0, s>>>(
         deg.data(), core.data(), rows, level, next_bm.data());
-    uint32_t qn = static_cast<uint32_t>(
-        compact_frontier(I, next_bm.data(), owned, g.v_begin, q.data(), s));
-    uint64_t global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+    uint64_t global_curr = 0;
+    uint32_t qn =
+        compact_frontier_global(I, comm_, world_, next_bm.data(), owned,
+                                g.v_begin, q.data(), s, global_curr);
     int level_rounds = 0;
     while (global_curr > 0) {
       if (qn) {
@@ -7231,44 +7075,26 @@ GpuRunResult GpuContext::peel(DeviceGraph& g, bool all_levels, int k,
         expand_frontier(
             I, view, q.data(), qn,
             KcoreOp{deg.data(), level, DevBitmap{next_bm.data()}, g.v_begin,
-                    g.v_end, multi, dec.data(),
-                    DevHalo{I.halo_idx.data(), I.halo_cnt.data(),
-                            DevBitmap{I.halo_bm.data()}, cap, view.slice,
-                            world_}},
+                    g.v_end, multi, dec.data(), halo},
             s);
       }
-      if (multi) {
-        uint64_t nrecv = halo_flush<uint32_t, true>(I, comm_, rank_, world_,
-                                                    dec.data(), cap, s);
-        if (nrecv)
-          halo_process_kernel<uint32_t, KcoreRecvOp>
-              <<<grid_for(nrecv), kBlock, 0, s>>>(
-                  reinterpret_cast<HaloPair<uint32_t>*>(I.recvbuf.data()),
-                  nrecv,
-                  KcoreRecvOp{deg.data(), level, DevBitmap{next_bm.data()},
-                              g.v_begin});
-      }
-      qn = static_cast<uint32_t>(
-          compact_frontier(I, next_bm.data(), owned, g.v_begin, q.data(), s));
-      global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+      if (multi)
+        halo_round<uint32_t, true>(
+            I, comm_, rank_, world_, dec.data(), cap,
+            KcoreRecvOp{deg.data(), level, DevBitmap{next_bm.data()},
+                        g.v_begin},
+            s);
+      qn = compact_frontier_global(I, comm_, world_, next_bm.data(), owned,
+                                   g.v_begin, q.data(), s, global_curr);
       ++level_rounds;
     }
     rounds += level_rounds;
     if (getenv("GRAPEHIP_DEBUG"))
       fprintf(stderr, "[kcore] level=%d subrounds=%d t=%.1fms\n", level,
-              level_rounds, (wall_s() - t0) * 1e3);
+              level_rounds, br.elapsed_ms());
     if (!all_levels) break;
   }
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = rounds;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = g.input_edges;
+  GpuRunResult res = br.finish(rounds, g.input_edges);
   if (fetch) {
     std::vector<int> c32(owned);
     if (owned)
@@ -7339,18 +7165,10 @@ GpuRunResult GpuContext::bc(DeviceGraph& g, int64_t source, bool fetch) {
   double* const coef = I.bc_coef.data();
   DeviceBuffer<uint32_t>& fdeg = I.trav_fdeg;
   DeviceBuffer<uint64_t>& foff = I.trav_foff;
-  if (multi) {
-    I.halo_idx.resize(static_cast<uint64_t>(world_) * cap);
-    I.halo_cnt.resize(world_);
-    I.halo_bm.resize((static_cast<uint64_t>(nv_pad) + 31) / 32);
-  }
-  const DevHalo halo{I.halo_idx.data(), I.halo_cnt.data(),
-                     DevBitmap{I.halo_bm.data()}, cap, view.slice, world_};
+  const DevHalo halo = halo_reserve(
+      I, world_, cap, view.slice, (static_cast<uint64_t>(nv_pad) + 31) / 32);
 
-  if (comm_) comm_->barrier();
-  HIP_CHECK(hipDeviceSynchronize());
-  double t0 = wall_s();
-  const uint64_t b_p2p0 = I.dc.bytes_p2p, b_coll0 = I.dc.bytes_coll;
+  RunBracket br(I, comm_);
 
   if (nv_pad) {
     HIP_CHECK(hipMemsetAsync(depth, 0xFF, static_cast<size_t>(nv_pad) * 4, s));
@@ -7358,10 +7176,7 @@ GpuRunResult GpuContext::bc(DeviceGraph& g, int64_t source, bool fetch) {
     HIP_CHECK(hipMemsetAsync(acc, 0, static_cast<size_t>(nv_pad) * 8, s));
   }
   HIP_CHECK(hipMemsetAsync(next_bm, 0, bm_words * 4, s));
-  if (multi) {
-    I.halo_cnt.zero(s);
-    I.halo_bm.zero(s);
-  }
+  if (multi) halo_reset(I, s);
   uint32_t src = map_source(g, source, s);
   if (src >= g.v_begin && src < g.v_end)
     bc_seed_kernel<<<1, 1, 0, s>>>(depth, sigma, src, g.v_begin, next_bm);
@@ -7369,41 +7184,28 @@ GpuRunResult GpuContext::bc(DeviceGraph& g, int64_t source, bool fetch) {
   // level_off[d] .. level_off[d + 1]: level d's slice of the order array.
   // Every owned vertex enters one frontier, so the slices fit in `owned`.
   std::vector<uint64_t> level_off{0};
-  uint32_t qn = static_cast<uint32_t>(
-      compact_frontier(I, next_bm, owned, g.v_begin, order, s));
-  uint64_t global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+  uint64_t global_curr = 0;
+  uint32_t qn = compact_frontier_global(I, comm_, world_, next_bm, owned,
+                                        g.v_begin, order, s, global_curr);
   uint32_t level = 0;
   while (global_curr > 0) {
     const uint32_t* q = order + level_off.back();
     level_off.push_back(level_off.back() + qn);
-    uint64_t fedges = 0;
-    if (qn) {
-      if (fdeg.size() < qn) fdeg.resize(qn + (qn >> 2) + 64);
-      if (foff.size() < qn + 1) foff.resize(qn + (qn >> 2) + 65);
-      gather_deg_kernel<<<grid_for(qn), kBlock, 0, s>>>(view, q, qn,
-                                                        fdeg.data());
-      fedges = exclusive_scan(fdeg.data(), foff.data(), qn, s, I.scan);
-    }
+    uint64_t fedges = scan_frontier_degrees(I, view, q, qn, fdeg, foff, s);
     launch_expand(I, view, q, qn, foff.data(), fedges,
                   BcFwdOp{depth, sigma, level + 1, DevBitmap{next_bm},
                           g.v_begin, g.v_end, multi, halo},
                   s);
-    if (multi) {
-      uint64_t nrecv = halo_flush<double, true>(I, comm_, rank_, world_,
-                                                sigma, cap, s);
-      if (nrecv)
-        halo_process_kernel<double, BcFwdRecvOp>
-            <<<grid_for(nrecv), kBlock, 0, s>>>(
-                reinterpret_cast<HaloPair<double>*>(I.recvbuf.data()), nrecv,
-                BcFwdRecvOp{depth, sigma, level + 1, DevBitmap{next_bm},
-                            g.v_begin});
-    }
-    qn = static_cast<uint32_t>(compact_frontier(
-        I, next_bm, owned, g.v_begin, order + level_off.back(), s));
-    global_curr = multi ? comm_->allreduce_sum(qn) : qn;
+    if (multi)
+      halo_round<double, true>(
+          I, comm_, rank_, world_, sigma, cap,
+          BcFwdRecvOp{depth, sigma, level + 1, DevBitmap{next_bm}, g.v_begin},
+          s);
+    qn = compact_frontier_global(I, comm_, world_, next_bm, owned, g.v_begin,
+                                 order + level_off.back(), s, global_curr);
     if (getenv("GRAPEHIP_DEBUG"))
       fprintf(stderr, "[bc] fwd level=%u fedges=%lu next=%u t=%.1fms\n",
-              level, (unsigned long)fedges, qn, (wall_s() - t0) * 1e3);
+              level, (unsigned long)fedges, qn, br.elapsed_ms());
     ++level;
   }
   const int levels = static_cast<int>(level);
@@ -7423,47 +7225,24 @@ GpuRunResult GpuContext::bc(DeviceGraph& g, int64_t source, bool fetch) {
                     BcBackOp{depth, coef, acc, static_cast<uint32_t>(d - 1),
                              g.v_begin, g.v_end, multi, halo},
                     s);
-    if (multi) {
-      uint64_t nrecv =
-          halo_flush<double, true>(I, comm_, rank_, world_, acc, cap, s);
-      if (nrecv)
-        halo_process_kernel<double, BcBackRecvOp>
-            <<<grid_for(nrecv), kBlock, 0, s>>>(
-                reinterpret_cast<HaloPair<double>*>(I.recvbuf.data()), nrecv,
-                BcBackRecvOp{acc});
-    }
+    if (multi)
+      halo_round<double, true>(I, comm_, rank_, world_, acc, cap,
+                               BcBackRecvOp{acc}, s);
     if (getenv("GRAPEHIP_DEBUG"))
       fprintf(stderr, "[bc] back level=%d slice=%u t=%.1fms\n", d, n,
-              (wall_s() - t0) * 1e3);
+              br.elapsed_ms());
   }
-  HIP_CHECK(hipDeviceSynchronize());
-  if (comm_) comm_->barrier();
-  double t1 = wall_s();
-
-  GpuRunResult res;
-  res.bytes_p2p = I.dc.bytes_p2p - b_p2p0;
-  res.bytes_coll = I.dc.bytes_coll - b_coll0;
-  res.rounds = levels;
-  res.seconds = comm_ ? comm_->allreduce_max_double(t1 - t0) : (t1 - t0);
-  res.traversed_edges = g.input_edges;
+  GpuRunResult res = br.finish(levels, g.input_edges);
   if (fetch) {
-    std::vector<uint32_t> d32(owned);
     res.f64.resize(owned);
     res.f64b.resize(owned);
     if (owned) {
-      HIP_CHECK(hipMemcpyAsync(d32.data(), depth + g.v_begin, owned * 4ull,
-                               hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipMemcpyAsync(res.f64.data(), acc + g.v_begin, owned * 8ull,
                                hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipMemcpyAsync(res.f64b.data(), sigma + g.v_begin,
                                owned * 8ull, hipMemcpyDeviceToHost, s));
     }
-    HIP_CHECK(hipStreamSynchronize(s));
-    res.i64.resize(owned);
-    for (uint32_t i = 0; i < owned; ++i)
-      res.i64[i] = d32[i] == 0xFFFFFFFFu
-                       ? std::numeric_limits<int64_t>::max()
-                       : static_cast<int64_t>(d32[i]);
+    res.i64 = fetch_depth_i64(depth, g, s);  // syncs s: all three landed
   }
   return res;
 }

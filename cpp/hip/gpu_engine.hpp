@@ -153,6 +153,12 @@ class GpuContext {
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device
   std::vector<uint64_t> debug_scan(const std::vector<uint32_t>& in);
+  // test hook: segmented sort of host CSR rows on the device; returns the
+  // sorted dst. w null: u32 keys; w given: (dst, weight) pairs, w sorted in
+  // place along with dst.
+  std::vector<uint32_t> debug_sort_rows(const std::vector<uint64_t>& off,
+                                        std::vector<uint32_t> dst,
+                                        std::vector<float>* w);
   // test hook: frontier-expansion launches so far per scheduler, in the
   // order cm, wm, strict, none (host-side count; expand_cm_range is no
   // scheduler choice and is not counted). reset zeroes them after the read.

@@ -5250,397 +5250,261 @@ __device__ __forceinline__ bool lcc_keep(uint32_t du, uint32_t u, uint32_t dv,
   return du > dv || (du == dv && u > v);
 }
 
-// --- pass 1: distinct neighbor count -------------------------------------
+// --- tiered dedup pass (passes 1 and 3 above) -----------------------------
+// Every tier walks a row of the combined (off1 [+ off2]) adjacency and sees
+// each u != v once; what happens on that first occurrence is the sink's:
+//   LccCountSink  counts them and writes D[v]
+//   LccEmitSink   appends them (orientation-filtered when `filter`) to the
+//                 row's capacity-layout slot in oadj and writes ocnt[r]
 
-__global__ void lcc_distinct_small_kernel(
-    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
-    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
-    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
-    uint32_t* __restrict__ D) {
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int wpb = kBlock / kWave;
-  size_t wstride = static_cast<size_t>(gridDim.x) * wpb;
-  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * wpb + wid; i < nrows;
-       i += wstride) {
-    uint32_t r = rows[i];
-    uint32_t v = v_begin + r;
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint32_t d1 = static_cast<uint32_t>(e1 - b1);
-    uint32_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += static_cast<uint32_t>(off2[r + 1] - b2);
-    }
-    uint32_t u = kCdlpEmpty;
-    if (lane < static_cast<int>(deg))
-      u = lane < static_cast<int>(d1) ? dst1[b1 + lane]
-                                      : dst2[b2 + (lane - d1)];
-    unsigned long long remaining =
-        __ballot(lane < static_cast<int>(deg) && u != v);
-    uint32_t distinct = 0;
-    while (remaining) {
-      int L = __ffsll(remaining) - 1;
-      uint32_t u0 = __shfl(u, L, 64);
-      remaining &= ~__ballot(u == u0);
-      ++distinct;
-    }
-    if (lane == 0) D[v] = distinct;
+// row r decoded; Len is u32 except in the large tier
+template <typename Len>
+struct LccRow {
+  uint32_t v;
+  uint64_t b1, b2;
+  Len d1, deg;
+  __device__ __forceinline__ uint32_t at(const uint32_t* __restrict__ dst1,
+                                         const uint32_t* __restrict__ dst2,
+                                         Len k) const {
+    return k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
+  }
+};
+
+template <typename Len>
+__device__ __forceinline__ LccRow<Len> lcc_row(
+    const uint64_t* __restrict__ off1, const uint64_t* __restrict__ off2,
+    uint32_t r, uint32_t v_begin) {
+  LccRow<Len> row;
+  row.v = v_begin + r;
+  row.b1 = off1[r];
+  row.d1 = static_cast<Len>(off1[r + 1] - row.b1);
+  row.deg = row.d1;
+  row.b2 = 0;
+  if (off2) {
+    row.b2 = off2[r];
+    row.deg += static_cast<Len>(off2[r + 1] - row.b2);
+  }
+  return row;
+}
+
+// open-addressing insert into a pow2 table (LDS: u32 mask, global: u64
+// mask); true iff u was not there yet
+template <typename Mask>
+__device__ __forceinline__ bool insert_once(uint32_t* table, Mask mask,
+                                            uint32_t u) {
+  Mask idx = cdlp_hash(u) & mask;
+  for (;;) {
+    uint32_t old = atomicCAS(&table[idx], kCdlpEmpty, u);
+    if (old == kCdlpEmpty) return true;
+    if (old == u) return false;
+    idx = (idx + 1) & mask;
   }
 }
 
-__global__ void lcc_distinct_mid_kernel(
-    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
-    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
-    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
-    uint32_t* __restrict__ D) {
-  __shared__ uint32_t s_lab[kLccLdsSlots];
-  __shared__ uint32_t s_distinct;
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
-    uint32_t r = rows[i];
-    uint32_t v = v_begin + r;
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint32_t d1 = static_cast<uint32_t>(e1 - b1);
-    uint32_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += static_cast<uint32_t>(off2[r + 1] - b2);
-    }
-    uint32_t cap = 64;
-    while (cap < 2 * deg) cap <<= 1;
-    if (cap > kLccLdsSlots) cap = kLccLdsSlots;
-    const uint32_t mask = cap - 1;
-    for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x)
-      s_lab[k] = kCdlpEmpty;
-    if (threadIdx.x == 0) s_distinct = 0;
-    __syncthreads();
-    for (uint32_t k = threadIdx.x; k < deg; k += blockDim.x) {
-      uint32_t u = k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
-      if (u == v) continue;
-      uint32_t idx = cdlp_hash(u) & mask;
-      for (;;) {
-        uint32_t old = atomicCAS(&s_lab[idx], kCdlpEmpty, u);
-        if (old == kCdlpEmpty) {
-          atomicAdd(&s_distinct, 1u);
-          break;
-        }
-        if (old == u) break;
-        idx = (idx + 1) & mask;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) D[v] = s_distinct;
-    __syncthreads();
-  }
+// LDS table size for a row: pow2 >= 2*deg, clamped to the tier's slots
+__device__ __forceinline__ uint32_t lcc_lds_cap(uint32_t deg,
+                                                uint32_t slots) {
+  uint32_t cap = 64;
+  while (cap < 2 * deg) cap <<= 1;
+  return cap > slots ? slots : cap;
 }
 
-__global__ void lcc_distinct_large_kernel(
-    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
-    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
-    const uint32_t* __restrict__ rows, uint64_t nrows,
-    const uint64_t* __restrict__ tbl_off, uint32_t* __restrict__ tbl_lab,
-    uint32_t v_begin, uint32_t* __restrict__ D) {
-  __shared__ uint32_t s_distinct;
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
-    uint32_t r = rows[i];
-    uint32_t v = v_begin + r;
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint64_t d1 = e1 - b1;
-    uint64_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += off2[r + 1] - b2;
-    }
-    uint64_t tb = tbl_off[i];
-    const uint64_t mask = (tbl_off[i + 1] - tb) - 1;
-    uint32_t* tl = tbl_lab + tb;
-    if (threadIdx.x == 0) s_distinct = 0;
-    __syncthreads();
-    for (uint64_t k = threadIdx.x; k < deg; k += blockDim.x) {
-      uint32_t u = k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
-      if (u == v) continue;
-      uint64_t idx = cdlp_hash(u) & mask;
-      for (;;) {
-        uint32_t old = atomicCAS(&tl[idx], kCdlpEmpty, u);
-        if (old == kCdlpEmpty) {
-          atomicAdd(&s_distinct, 1u);
-          break;
-        }
-        if (old == u) break;
-        idx = (idx + 1) & mask;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) D[v] = s_distinct;
-    __syncthreads();
+// small tier (deg <= 64, one lane per arc): bit L set iff lane L holds the
+// first occurrence of its value among the active lanes
+__device__ __forceinline__ unsigned long long lcc_first_mask(uint32_t u,
+                                                             bool active) {
+  unsigned long long remaining = __ballot(active);
+  unsigned long long first_mask = 0;
+  while (remaining) {
+    int L = __ffsll(remaining) - 1;
+    uint32_t u0 = __shfl(u, L, 64);
+    first_mask |= (1ull << L);
+    remaining &= ~__ballot(active && u == u0);
   }
+  return first_mask;
 }
 
-// 4-rows-per-block wave variants for 64 < deg <= kCdlpWaveDeg (a block-
-// per-row hash on a deg-100 row idles 3 of 4 waves; same uniform-barrier
-// staging as cdlp_wave_kernel)
-__global__ void lcc_distinct_wave_kernel(
-    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
-    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
-    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
-    uint32_t* __restrict__ D) {
-  __shared__ uint32_t s_lab[4][kCdlpWaveSlots];
-  __shared__ uint32_t s_distinct[4];
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  uint64_t groups = (nrows + 3) / 4;
-  for (uint64_t grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-    uint64_t i = grp * 4 + wid;
-    const bool have = i < nrows;
-    uint32_t r = have ? rows[i] : 0;
-    uint32_t v = v_begin + r;
-    uint32_t d1 = 0, deg = 0, cap = 64, mask = 63;
-    uint64_t b1 = 0, b2 = 0;
-    if (have) {
-      b1 = off1[r];
-      d1 = static_cast<uint32_t>(off1[r + 1] - b1);
-      deg = d1;
-      if (off2) {
-        b2 = off2[r];
-        deg += static_cast<uint32_t>(off2[r + 1] - b2);
-      }
-      while (cap < 2 * deg) cap <<= 1;
-      if (cap > kCdlpWaveSlots) cap = kCdlpWaveSlots;
-      mask = cap - 1;
-      for (uint32_t k = lane; k < cap; k += kWave)
-        s_lab[wid][k] = kCdlpEmpty;
-      if (lane == 0) s_distinct[wid] = 0;
-    }
-    __syncthreads();
-    if (have) {
-      for (uint32_t k = lane; k < deg; k += kWave) {
-        uint32_t u = k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
-        if (u == v) continue;
-        uint32_t idx = cdlp_hash(u) & mask;
-        for (;;) {
-          uint32_t old = atomicCAS(&s_lab[wid][idx], kCdlpEmpty, u);
-          if (old == kCdlpEmpty) {
-            atomicAdd(&s_distinct[wid], 1u);
-            break;
-          }
-          if (old == u) break;
-          idx = (idx + 1) & mask;
-        }
-      }
-    }
-    __syncthreads();
-    if (have && lane == 0) D[v] = s_distinct[wid];
-    __syncthreads();
+// A sink supplies: Row open(r, v) once the row's counter n is zeroed;
+// first(row, u, v, &n) on a first occurrence (n is the tier's LDS counter);
+// close(r, v, n) by one thread when the row is done; and small(...) for the
+// table-less tier, called by the whole wave with the first-occurrence mask.
+struct LccCountSink {
+  uint32_t* D;
+  struct Row {};
+  __device__ __forceinline__ Row open(uint32_t, uint32_t) const { return {}; }
+  __device__ __forceinline__ void first(const Row&, uint32_t, uint32_t,
+                                        uint32_t* n) const {
+    atomicAdd(n, 1u);
   }
-}
-
-__global__ void lcc_orient_wave_kernel(
-    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
-    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
-    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
-    const uint32_t* __restrict__ D, const uint64_t* __restrict__ ooff,
-    uint32_t* __restrict__ oadj, uint32_t* __restrict__ ocnt, bool filter) {
-  __shared__ uint32_t s_lab[4][kCdlpWaveSlots];
-  __shared__ uint32_t s_cursor[4];
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  uint64_t groups = (nrows + 3) / 4;
-  for (uint64_t grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-    uint64_t i = grp * 4 + wid;
-    const bool have = i < nrows;
-    uint32_t r = have ? rows[i] : 0;
-    uint32_t v = v_begin + r;
-    uint32_t d1 = 0, deg = 0, cap = 64, mask = 63;
-    uint64_t b1 = 0, b2 = 0;
-    if (have) {
-      b1 = off1[r];
-      d1 = static_cast<uint32_t>(off1[r + 1] - b1);
-      deg = d1;
-      if (off2) {
-        b2 = off2[r];
-        deg += static_cast<uint32_t>(off2[r + 1] - b2);
-      }
-      while (cap < 2 * deg) cap <<= 1;
-      if (cap > kCdlpWaveSlots) cap = kCdlpWaveSlots;
-      mask = cap - 1;
-      for (uint32_t k = lane; k < cap; k += kWave)
-        s_lab[wid][k] = kCdlpEmpty;
-      if (lane == 0) s_cursor[wid] = 0;
-    }
-    __syncthreads();
-    if (have) {
-      uint32_t dv = D[v];
-      uint64_t base = ooff[r];
-      for (uint32_t k = lane; k < deg; k += kWave) {
-        uint32_t u = k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
-        if (u == v) continue;
-        uint32_t idx = cdlp_hash(u) & mask;
-        for (;;) {
-          uint32_t old = atomicCAS(&s_lab[wid][idx], kCdlpEmpty, u);
-          if (old == kCdlpEmpty) {
-            if (!filter || lcc_keep(D[u], u, dv, v))
-              oadj[base + atomicAdd(&s_cursor[wid], 1u)] = u;
-            break;
-          }
-          if (old == u) break;
-          idx = (idx + 1) & mask;
-        }
-      }
-    }
-    __syncthreads();
-    if (have && lane == 0) ocnt[r] = s_cursor[wid];
-    __syncthreads();
+  __device__ __forceinline__ void close(uint32_t, uint32_t v,
+                                        uint32_t n) const {
+    D[v] = n;
   }
-}
+  __device__ __forceinline__ void small(uint32_t, uint32_t v, int lane,
+                                        uint32_t, bool,
+                                        unsigned long long first_mask) const {
+    if (lane == 0) D[v] = __popcll(first_mask);
+  }
+};
 
-// --- pass 2: build oriented adjacency (dedup + orientation filter) --------
-
-__global__ void lcc_orient_small_kernel(
-    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
-    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
-    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
-    const uint32_t* __restrict__ D, const uint64_t* __restrict__ ooff,
-    uint32_t* __restrict__ oadj, uint32_t* __restrict__ ocnt, bool filter) {
-  const int lane = threadIdx.x & 63;
-  const int wid = threadIdx.x >> 6;
-  const int wpb = kBlock / kWave;
-  size_t wstride = static_cast<size_t>(gridDim.x) * wpb;
-  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * wpb + wid; i < nrows;
-       i += wstride) {
-    uint32_t r = rows[i];
-    uint32_t v = v_begin + r;
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint32_t d1 = static_cast<uint32_t>(e1 - b1);
-    uint32_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += static_cast<uint32_t>(off2[r + 1] - b2);
-    }
-    uint32_t u = kCdlpEmpty;
-    if (lane < static_cast<int>(deg))
-      u = lane < static_cast<int>(d1) ? dst1[b1 + lane]
-                                      : dst2[b2 + (lane - d1)];
-    bool active = lane < static_cast<int>(deg) && u != v;
-    // first-occurrence mask (wave dedup): the lowest lane holding each
-    // distinct value is its representative
-    unsigned long long remaining = __ballot(active);
-    unsigned long long first_mask = 0;
-    while (remaining) {
-      int L = __ffsll(remaining) - 1;
-      uint32_t u0 = __shfl(u, L, 64);
-      unsigned long long m = __ballot(active && u == u0);
-      first_mask |= (1ull << L);
-      remaining &= ~m;
-    }
-    uint32_t dv = D[v];
-    bool keep = active && ((first_mask >> lane) & 1) &&
-                (!filter || lcc_keep(D[u], u, dv, v));
+struct LccEmitSink {
+  const uint32_t* D;
+  const uint64_t* ooff;
+  uint32_t* oadj;
+  uint32_t* ocnt;
+  bool filter;
+  struct Row {
+    uint32_t dv;
+    uint64_t base;
+  };
+  __device__ __forceinline__ Row open(uint32_t r, uint32_t v) const {
+    return {D[v], ooff[r]};
+  }
+  __device__ __forceinline__ bool wants(const Row& row, uint32_t u,
+                                        uint32_t v) const {
+    return !filter || lcc_keep(D[u], u, row.dv, v);
+  }
+  __device__ __forceinline__ void first(const Row& row, uint32_t u,
+                                        uint32_t v, uint32_t* n) const {
+    if (wants(row, u, v)) oadj[row.base + atomicAdd(n, 1u)] = u;
+  }
+  __device__ __forceinline__ void close(uint32_t r, uint32_t,
+                                        uint32_t n) const {
+    ocnt[r] = n;
+  }
+  __device__ __forceinline__ void small(uint32_t r, uint32_t v, int lane,
+                                        uint32_t u, bool active,
+                                        unsigned long long first_mask) const {
+    Row row = open(r, v);
+    bool keep = active && ((first_mask >> lane) & 1) && wants(row, u, v);
     unsigned long long keep_mask = __ballot(keep);
     uint32_t pos = __popcll(keep_mask & ((1ull << lane) - 1));
-    uint64_t base = ooff[r];
-    if (keep) oadj[base + pos] = u;
+    if (keep) oadj[row.base + pos] = u;
     if (lane == 0) ocnt[r] = __popcll(keep_mask);
   }
-}
+};
 
-__global__ void lcc_orient_mid_kernel(
+template <typename Sink>
+__global__ void lcc_dedup_small_kernel(
     const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
     const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
     const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
-    const uint32_t* __restrict__ D, const uint64_t* __restrict__ ooff,
-    uint32_t* __restrict__ oadj, uint32_t* __restrict__ ocnt, bool filter) {
-  __shared__ uint32_t s_lab[kLccLdsSlots];
-  __shared__ uint32_t s_cursor;
-  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
+    Sink sink) {
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int wpb = kBlock / kWave;
+  size_t wstride = static_cast<size_t>(gridDim.x) * wpb;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * wpb + wid; i < nrows;
+       i += wstride) {
     uint32_t r = rows[i];
-    uint32_t v = v_begin + r;
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint32_t d1 = static_cast<uint32_t>(e1 - b1);
-    uint32_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += static_cast<uint32_t>(off2[r + 1] - b2);
+    LccRow<uint32_t> row = lcc_row<uint32_t>(off1, off2, r, v_begin);
+    uint32_t u = kCdlpEmpty;
+    if (lane < static_cast<int>(row.deg))
+      u = row.at(dst1, dst2, static_cast<uint32_t>(lane));
+    bool active = lane < static_cast<int>(row.deg) && u != row.v;
+    sink.small(r, row.v, lane, u, active, lcc_first_mask(u, active));
+  }
+}
+
+// 4 rows per block for 64 < deg <= kCdlpWaveDeg (a block-per-row hash on a
+// deg-100 row idles 3 of 4 waves; same uniform-barrier staging as
+// cdlp_wave_kernel)
+template <typename Sink>
+__global__ void lcc_dedup_wave_kernel(
+    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
+    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
+    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
+    Sink sink) {
+  __shared__ uint32_t s_lab[4][kCdlpWaveSlots];
+  __shared__ uint32_t s_n[4];
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  uint64_t groups = (nrows + 3) / 4;
+  for (uint64_t grp = blockIdx.x; grp < groups; grp += gridDim.x) {
+    uint64_t i = grp * 4 + wid;
+    const bool have = i < nrows;
+    uint32_t r = have ? rows[i] : 0;
+    LccRow<uint32_t> row{};
+    uint32_t mask = 63;
+    if (have) {
+      row = lcc_row<uint32_t>(off1, off2, r, v_begin);
+      uint32_t cap = lcc_lds_cap(row.deg, kCdlpWaveSlots);
+      mask = cap - 1;
+      for (uint32_t k = lane; k < cap; k += kWave)
+        s_lab[wid][k] = kCdlpEmpty;
+      if (lane == 0) s_n[wid] = 0;
     }
-    uint32_t cap = 64;
-    while (cap < 2 * deg) cap <<= 1;
-    if (cap > kLccLdsSlots) cap = kLccLdsSlots;
-    const uint32_t mask = cap - 1;
-    for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x)
-      s_lab[k] = kCdlpEmpty;
-    if (threadIdx.x == 0) s_cursor = 0;
     __syncthreads();
-    uint32_t dv = D[v];
-    uint64_t base = ooff[r];
-    for (uint32_t k = threadIdx.x; k < deg; k += blockDim.x) {
-      uint32_t u = k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
-      if (u == v) continue;
-      uint32_t idx = cdlp_hash(u) & mask;
-      for (;;) {
-        uint32_t old = atomicCAS(&s_lab[idx], kCdlpEmpty, u);
-        if (old == kCdlpEmpty) {
-          if (!filter || lcc_keep(D[u], u, dv, v))
-            oadj[base + atomicAdd(&s_cursor, 1u)] = u;
-          break;
-        }
-        if (old == u) break;
-        idx = (idx + 1) & mask;
+    if (have) {
+      auto st = sink.open(r, row.v);
+      for (uint32_t k = lane; k < row.deg; k += kWave) {
+        uint32_t u = row.at(dst1, dst2, k);
+        if (u == row.v) continue;
+        if (insert_once(s_lab[wid], mask, u))
+          sink.first(st, u, row.v, &s_n[wid]);
       }
     }
     __syncthreads();
-    if (threadIdx.x == 0) ocnt[r] = s_cursor;
+    if (have && lane == 0) sink.close(r, row.v, s_n[wid]);
     __syncthreads();
   }
 }
 
-__global__ void lcc_orient_large_kernel(
+template <typename Sink>
+__global__ void lcc_dedup_mid_kernel(
+    const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
+    const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
+    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
+    Sink sink) {
+  __shared__ uint32_t s_lab[kLccLdsSlots];
+  __shared__ uint32_t s_n;
+  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
+    uint32_t r = rows[i];
+    LccRow<uint32_t> row = lcc_row<uint32_t>(off1, off2, r, v_begin);
+    const uint32_t cap = lcc_lds_cap(row.deg, kLccLdsSlots);
+    const uint32_t mask = cap - 1;
+    for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x)
+      s_lab[k] = kCdlpEmpty;
+    if (threadIdx.x == 0) s_n = 0;
+    __syncthreads();
+    auto st = sink.open(r, row.v);
+    for (uint32_t k = threadIdx.x; k < row.deg; k += blockDim.x) {
+      uint32_t u = row.at(dst1, dst2, k);
+      if (u == row.v) continue;
+      if (insert_once(s_lab, mask, u)) sink.first(st, u, row.v, &s_n);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) sink.close(r, row.v, s_n);
+    __syncthreads();
+  }
+}
+
+// rows past kCdlpMidDeg: row i hashes into its slice of the global table
+// pool (tbl_off[i] .. tbl_off[i + 1]), which the host clears before launch
+template <typename Sink>
+__global__ void lcc_dedup_large_kernel(
     const uint64_t* __restrict__ off1, const uint32_t* __restrict__ dst1,
     const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
     const uint32_t* __restrict__ rows, uint64_t nrows,
     const uint64_t* __restrict__ tbl_off, uint32_t* __restrict__ tbl_lab,
-    uint32_t v_begin, const uint32_t* __restrict__ D,
-    const uint64_t* __restrict__ ooff, uint32_t* __restrict__ oadj,
-    uint32_t* __restrict__ ocnt, bool filter) {
-  __shared__ uint32_t s_cursor;
+    uint32_t v_begin, Sink sink) {
+  __shared__ uint32_t s_n;
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
-    uint32_t v = v_begin + r;
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint64_t d1 = e1 - b1;
-    uint64_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += off2[r + 1] - b2;
-    }
+    LccRow<uint64_t> row = lcc_row<uint64_t>(off1, off2, r, v_begin);
     uint64_t tb = tbl_off[i];
     const uint64_t mask = (tbl_off[i + 1] - tb) - 1;
     uint32_t* tl = tbl_lab + tb;
-    if (threadIdx.x == 0) s_cursor = 0;
+    if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
-    uint32_t dv = D[v];
-    uint64_t base = ooff[r];
-    for (uint64_t k = threadIdx.x; k < deg; k += blockDim.x) {
-      uint32_t u = k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
-      if (u == v) continue;
-      uint64_t idx = cdlp_hash(u) & mask;
-      for (;;) {
-        uint32_t old = atomicCAS(&tl[idx], kCdlpEmpty, u);
-        if (old == kCdlpEmpty) {
-          if (!filter || lcc_keep(D[u], u, dv, v))
-            oadj[base + atomicAdd(&s_cursor, 1u)] = u;
-          break;
-        }
-        if (old == u) break;
-        idx = (idx + 1) & mask;
-      }
+    auto st = sink.open(r, row.v);
+    for (uint64_t k = threadIdx.x; k < row.deg; k += blockDim.x) {
+      uint32_t u = row.at(dst1, dst2, k);
+      if (u == row.v) continue;
+      if (insert_once(tl, mask, u)) sink.first(st, u, row.v, &s_n);
     }
     __syncthreads();
-    if (threadIdx.x == 0) ocnt[r] = s_cursor;
+    if (threadIdx.x == 0) sink.close(r, row.v, s_n);
     __syncthreads();
   }
 }
@@ -5704,15 +5568,8 @@ __global__ void lcc_hashfill_kernel(const uint64_t* __restrict__ goff,
     uint64_t hb = hoff[v];
     const uint64_t mask = (hoff[v + 1] - hb) - 1;
     uint32_t* t = htab + hb;
-    for (uint32_t k = lane; k < n; k += kWave) {
-      uint32_t x = gdst[b + k];
-      uint64_t idx = cdlp_hash(x) & mask;
-      for (;;) {
-        uint32_t old = atomicCAS(&t[idx], kCdlpEmpty, x);
-        if (old == kCdlpEmpty || old == x) break;
-        idx = (idx + 1) & mask;
-      }
-    }
+    for (uint32_t k = lane; k < n; k += kWave)
+      (void)insert_once(t, mask, gdst[b + k]);
   }
 }
 
@@ -5913,11 +5770,13 @@ __global__ void lcc_tri_staged_kernel(
   }
 }
 
-// bucket rows for the two light tiers (skips empty rows)
-__global__ void lcc_tribucket_kernel(const uint64_t* __restrict__ goff,
-                                     uint32_t owned, uint32_t v_begin,
-                                     uint32_t* wee, unsigned long long* cw,
-                                     uint32_t* big, unsigned long long* cb) {
+// bucket rows for the two light tiers; rows shorter than min_n are skipped
+// (1 undirected: empty rows; 2 directed: a lone neighbor closes no pair)
+__global__ void lcc_bucket_kernel(const uint64_t* __restrict__ goff,
+                                  uint32_t owned, uint32_t v_begin,
+                                  uint32_t min_n, uint32_t* wee,
+                                  unsigned long long* cw, uint32_t* big,
+                                  unsigned long long* cb) {
   __shared__ uint32_t s_cnt[2];
   __shared__ unsigned long long s_base[2];
   uint32_t* lists[2] = {wee, big};
@@ -5932,7 +5791,7 @@ __global__ void lcc_tribucket_kernel(const uint64_t* __restrict__ goff,
     uint32_t loc = 0;
     if (r < owned) {
       uint64_t n = goff[v_begin + r + 1] - goff[v_begin + r];
-      if (n) {
+      if (n >= min_n) {
         b = n <= kLccWeeRows ? 0 : 1;
         loc = atomicAdd(&s_cnt[b], 1u);
       }
@@ -6035,41 +5894,6 @@ __global__ void lcc_triangle_heavy_kernel(
 // (no orientation trick applies to the directed definition). Same light
 // tiers as the undirected counter: wee rows wave-per-row with global
 // probes; bigger rows block-per-row with U(v)'s hash set staged in LDS.
-__global__ void lcc_dir_bucket_kernel(const uint64_t* __restrict__ goffU,
-                                      uint32_t owned, uint32_t v_begin,
-                                      uint32_t* wee, unsigned long long* cw,
-                                      uint32_t* big,
-                                      unsigned long long* cb) {
-  __shared__ uint32_t s_cnt[2];
-  __shared__ unsigned long long s_base[2];
-  uint32_t* lists[2] = {wee, big};
-  unsigned long long* gcnt[2] = {cw, cb};
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < owned;
-       base += stride) {
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t r = base + threadIdx.x;
-    int b = -1;
-    uint32_t loc = 0;
-    if (r < owned) {
-      uint64_t n = goffU[v_begin + r + 1] - goffU[v_begin + r];
-      if (n >= 2) {
-        b = n <= kLccWeeRows ? 0 : 1;
-        loc = atomicAdd(&s_cnt[b], 1u);
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x])
-      s_base[threadIdx.x] =
-          atomicAdd(gcnt[threadIdx.x],
-                    static_cast<unsigned long long>(s_cnt[threadIdx.x]));
-    __syncthreads();
-    if (b >= 0) lists[b][s_base[b] + loc] = r;
-    __syncthreads();
-  }
-}
-
 __global__ void lcc_dir_count_wee_kernel(
     const uint64_t* __restrict__ goffU, const uint32_t* __restrict__ gdstU,
     const uint64_t* __restrict__ hoffU, const uint32_t* __restrict__ htabU,
@@ -6236,38 +6060,25 @@ __global__ void lcc_outcap_kernel(const uint64_t* __restrict__ off,
   }
 }
 
-__global__ void lcc_dir_finalize_kernel(
-    const unsigned long long* __restrict__ T,
-    const uint32_t* __restrict__ D, uint32_t owned, uint32_t v_begin,
-    double* __restrict__ lcc) {
-  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < owned;
-       r += stride) {
-    uint32_t d = D[v_begin + r];
-    lcc[r] = d < 2 ? 0.0
-                   : static_cast<double>(T[v_begin + r]) /
-                         (static_cast<double>(d) * (d - 1));
-  }
-}
-
+// lcc = scale * T / (D (D - 1)): scale 2.0 undirected (T = triangles at v,
+// over unordered neighbor pairs), 1.0 directed (T = arcs among N(v), over
+// ordered pairs)
 __global__ void lcc_finalize_kernel(const unsigned long long* __restrict__ T,
                                     const uint32_t* __restrict__ D,
                                     uint32_t owned, uint32_t v_begin,
-                                    double* __restrict__ lcc) {
+                                    double scale, double* __restrict__ lcc) {
   size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < owned;
        r += stride) {
     uint32_t d = D[v_begin + r];
     lcc[r] = d < 2 ? 0.0
-                   : 2.0 * static_cast<double>(T[v_begin + r]) /
+                   : scale * static_cast<double>(T[v_begin + r]) /
                          (static_cast<double>(d) * (d - 1));
   }
 }
 
 namespace {
 
-// Shared piece: turn capacity-layout per-owned-row lists into a replicated
-// global CSR (allgather counts -> scan -> compact -> per-rank broadcast).
 // mark remote dsts of the capacity-layout oriented adjacency (wave/row)
 __global__ void lcc_mark_oriented_kernel(
     const uint64_t* __restrict__ ooff, const uint32_t* __restrict__ ocnt,
@@ -6359,17 +6170,131 @@ void lcc_fetch_referenced_rows(GpuContext::Impl& I,
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// Compact a capacity-layout family into a sparse global-index CSR. With
-// lists (multi): counts are synced over the request lists and referenced
-// remote rows fetched (volume scales with the boundary). Without lists:
-// own rows only — for families that are never probed at remote indices
-// (directed U, read only at owned v).
-void build_global_csr(GpuContext::Impl& I, int rank, int world,
-                      uint32_t nv_pad, uint32_t slice, uint32_t owned,
-                      uint32_t v_begin, const DeviceBuffer<uint64_t>& ooff,
-                      const DeviceBuffer<uint32_t>& ocnt,
-                      const DeviceBuffer<uint32_t>& oadj,
-                      GlobalDedupCsr& out, hipStream_t s,
+// --- set-building helpers, in call order: tiers -> distinct -> emit ->
+// global CSR -> hash sets ------------------------------------------------
+
+// Owned rows split by combined (off1 [+ off2]) degree, reusing the CDLP
+// bucketer, and the global table pool the large tier hashes into.
+struct LccTiers {
+  DeviceBuffer<uint32_t> small, wave, mid, large;
+  uint64_t n_small = 0, n_wave = 0, n_mid = 0, n_large = 0;
+  DeviceBuffer<uint64_t> heavy_off;  // per large row, into tbl_lab
+  DeviceBuffer<uint32_t> tbl_lab;
+  uint64_t heavy_total = 0;
+};
+
+LccTiers build_lcc_tiers(GpuContext::Impl& I, const uint64_t* off1,
+                         const uint64_t* off2, uint32_t owned,
+                         hipStream_t s) {
+  LccTiers t;
+  t.small.resize(owned ? owned : 1);
+  t.wave.resize(owned ? owned : 1);
+  t.mid.resize(owned ? owned : 1);
+  t.large.resize(owned ? owned : 1);
+  DeviceBuffer<unsigned long long> cnts(5);
+  cnts.zero(s);
+  if (owned)
+    cdlp_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+        off1, off2, owned, nullptr, cnts.data() + 3, t.small.data(),
+        cnts.data() + 0, t.wave.data(), cnts.data() + 4, t.mid.data(),
+        cnts.data() + 1, t.large.data(), cnts.data() + 2);
+  auto hc = cnts.download(s);
+  t.n_small = hc[0], t.n_mid = hc[1], t.n_large = hc[2], t.n_wave = hc[4];
+  if (t.n_large) {
+    DeviceBuffer<uint32_t> heavy_caps(t.n_large);
+    t.heavy_off.resize(t.n_large + 1);
+    cdlp_heavy_cap_kernel<<<grid_for(t.n_large), kBlock, 0, s>>>(
+        off1, off2, t.large.data(), t.n_large, heavy_caps.data());
+    t.heavy_total = exclusive_scan(heavy_caps.data(), t.heavy_off.data(),
+                                   t.n_large, s, I.scan);
+    t.tbl_lab.resize(t.heavy_total);
+  }
+  return t;
+}
+
+// one dedup pass of (o1,d1[,o2,d2]) over all four tiers into `sink`
+template <typename Sink>
+void launch_dedup_tiers(LccTiers& t, const uint64_t* o1, const uint32_t* d1,
+                        const uint64_t* o2, const uint32_t* d2,
+                        uint32_t v_begin, Sink sink, hipStream_t s) {
+  if (t.n_small)
+    lcc_dedup_small_kernel<<<grid_for(t.n_small * kWave), kBlock, 0, s>>>(
+        o1, d1, o2, d2, t.small.data(), t.n_small, v_begin, sink);
+  if (t.n_wave)
+    lcc_dedup_wave_kernel<<<grid_for(((t.n_wave + 3) / 4) * kBlock), kBlock,
+                            0, s>>>(o1, d1, o2, d2, t.wave.data(), t.n_wave,
+                                    v_begin, sink);
+  if (t.n_mid)
+    lcc_dedup_mid_kernel<<<std::min<int>(t.n_mid, kMaxGrid), kBlock, 0, s>>>(
+        o1, d1, o2, d2, t.mid.data(), t.n_mid, v_begin, sink);
+  if (t.n_large) {
+    fill(t.tbl_lab.data(), kCdlpEmpty, t.heavy_total, s);
+    lcc_dedup_large_kernel<<<std::min<int>(t.n_large, kMaxGrid), kBlock, 0,
+                             s>>>(o1, d1, o2, d2, t.large.data(), t.n_large,
+                                  t.heavy_off.data(), t.tbl_lab.data(),
+                                  v_begin, sink);
+  }
+}
+
+// Dv[v] = |distinct neighbors of v, excl. self| for owned v (global index).
+// Multi: the emit filter reads Dv[dst] for local dsts only, so referenced
+// entries are refreshed point-to-point instead of allgathering slices.
+void lcc_degree_pass(GpuContext::Impl& I, DeviceGraph& g, LccTiers& t,
+                       const uint64_t* o1, const uint32_t* d1,
+                       const uint64_t* o2, const uint32_t* d2,
+                       uint32_t nv_pad, bool multi,
+                       DeviceBuffer<uint32_t>& Dv, hipStream_t s) {
+  Dv.resize(nv_pad);
+  Dv.zero(s);
+  launch_dedup_tiers(t, o1, d1, o2, d2, g.v_begin, LccCountSink{Dv.data()},
+                     s);
+  if (multi) {
+    mirror_sync_begin(I, g, Dv.data(), s);
+    mirror_sync_end(I, g, Dv.data(), s);
+  }
+}
+
+// per-owned-row lists in capacity layout: row r holds ocnt[r] entries at
+// oadj[ooff[r]..], with room for caps[r]
+struct CapRows {
+  DeviceBuffer<uint64_t> ooff;
+  DeviceBuffer<uint32_t> oadj, ocnt;
+};
+
+// Deduped neighbor lists of (o1,d1[,o2,d2]) in capacity layout; `filter`
+// keeps only the oriented side, (D[u],u) > (D[v],v). The tiers may come
+// from a wider family (directed O reuses the combined-degree tiers): a row
+// only has to fit the tier it sits in.
+CapRows lcc_emit_pass(GpuContext::Impl& I, LccTiers& t, const uint64_t* o1,
+                      const uint32_t* d1, const uint64_t* o2,
+                      const uint32_t* d2, const DeviceBuffer<uint32_t>& caps,
+                      bool filter, const DeviceBuffer<uint32_t>& Dv,
+                      uint32_t owned, uint32_t v_begin, hipStream_t s) {
+  CapRows rows;
+  rows.ooff.resize(owned + 1);
+  uint64_t cap_total =
+      exclusive_scan(caps.data(), rows.ooff.data(), owned, s, I.scan);
+  rows.oadj.resize(cap_total ? cap_total : 1);
+  rows.ocnt.resize(owned ? owned : 1);
+  rows.ocnt.zero(s);
+  launch_dedup_tiers(t, o1, d1, o2, d2, v_begin,
+                     LccEmitSink{Dv.data(), rows.ooff.data(),
+                                 rows.oadj.data(), rows.ocnt.data(), filter},
+                     s);
+  return rows;
+}
+
+// Compact a capacity-layout family into a sparse global-index CSR, taking
+// the rows over so oadj is gone before any sort scratch or fetch staging
+// is allocated. sort_owned sorts the owned rows ascending before peers
+// fetch them. With lists (multi): counts are synced over the request lists
+// and referenced remote rows fetched (volume scales with the boundary).
+// Without lists: own rows only — for families that are never probed at
+// remote indices (directed U, read only at owned v).
+void build_global_csr(GpuContext::Impl& I, int world, uint32_t nv_pad,
+                      uint32_t slice, uint32_t owned, uint32_t v_begin,
+                      CapRows rows, bool sort_owned, GlobalDedupCsr& out,
+                      hipStream_t s,
                       const DeviceBuffer<uint32_t>* ridx = nullptr,
                       const std::vector<uint64_t>* roff = nullptr,
                       const DeviceBuffer<uint32_t>* sidx = nullptr,
@@ -6377,9 +6302,11 @@ void build_global_csr(GpuContext::Impl& I, int rank, int world,
   bool fetch = world > 1 && ridx;
   out.gcnt.resize(nv_pad);
   out.gcnt.zero(s);
-  HIP_CHECK(hipMemcpyAsync(out.gcnt.data() + v_begin, ocnt.data(),
+  HIP_CHECK(hipMemcpyAsync(out.gcnt.data() + v_begin, rows.ocnt.data(),
                            owned * 4, hipMemcpyDeviceToDevice, s));
   if (fetch) {
+    // unfetched rows keep a zero count, so they scan to zero length and
+    // the fetch regions stay contiguous per owner
     DeviceBuffer<uint8_t> ss((*soff)[world] * 4 + 4),
         sr(roff->back() * 4 + 4);
     ref_sync_begin(I, *sidx, *soff, *roff, ss, sr, out.gcnt.data(), s);
@@ -6391,15 +6318,19 @@ void build_global_csr(GpuContext::Impl& I, int rank, int world,
   out.gdst.resize(out.total ? out.total : 1);
   if (owned)
     lcc_compact_kernel<<<grid_for(static_cast<size_t>(owned) * kWave),
-                         kBlock, 0, s>>>(ooff.data(), ocnt.data(),
-                                         oadj.data(), out.goff.data(),
+                         kBlock, 0, s>>>(rows.ooff.data(), rows.ocnt.data(),
+                                         rows.oadj.data(), out.goff.data(),
                                          owned, v_begin, out.gdst.data());
+  rows.oadj.free();
+  if (sort_owned)
+    segmented_sort_rows(out.goff.data() + v_begin, owned,
+                        U32KeyCodec{out.gdst.data()}, s, I.scan);
   if (fetch)
     lcc_fetch_referenced_rows(I, *sidx, *soff, out.gcnt, out.goff,
                               out.gdst, slice, nv_pad, world, s);
-  (void)rank;
 }
 
+// per-vertex open-addressing sets over a global CSR (capacity 2x, pow2)
 void build_hash_sets(GpuContext::Impl& I, uint32_t nv_pad,
                      const GlobalDedupCsr& csr, DeviceBuffer<uint64_t>& hoff,
                      DeviceBuffer<uint32_t>& htab, hipStream_t s) {
@@ -6410,11 +6341,95 @@ void build_hash_sets(GpuContext::Impl& I, uint32_t nv_pad,
                                                          hcap.data());
   uint64_t total = exclusive_scan(hcap.data(), hoff.data(), nv_pad, s,
                                   I.scan);
+  hcap.free();
   htab.resize(total);
   fill(htab.data(), kCdlpEmpty, total, s);
   lcc_hashfill_kernel<<<grid_for(static_cast<size_t>(nv_pad) * kWave),
                         kBlock, 0, s>>>(csr.goff.data(), csr.gdst.data(),
                                         hoff.data(), nv_pad, htab.data());
+}
+
+// --- counting tail shared by both variants ------------------------------
+// begin: credits T, the deferred-edge queue, and the owned rows of `goff`
+// bucketed into the two light tiers. The caller launches its own light
+// kernels, reads the queue length back with lcc_heavy_count, launches its
+// heavy kernel, and ends with lcc_finish.
+struct LccTail {
+  DeviceBuffer<unsigned long long> Tcnt;
+  uint32_t heavy_thresh = 48;
+  DeviceBuffer<unsigned long long> heavy_q, heavy_n;
+  DeviceBuffer<uint32_t> wee_rows, big_rows;
+  uint64_t n_wee = 0, n_big = 0;
+};
+
+LccTail lcc_tail_begin(DeviceGraph& g, uint32_t nv_pad,
+                       const DeviceBuffer<uint64_t>& goff, uint32_t min_n,
+                       hipStream_t s) {
+  uint32_t owned = g.owned();
+  LccTail t;
+  t.Tcnt.resize(nv_pad);
+  t.Tcnt.zero(s);
+  // min-side size above which an edge defers to the wave-per-edge pass;
+  // 96 -> 48 after the two-box sweep + clean full-scale re-measurement
+  // (profiles/r01_lcc_heavy_thresh_sweep.md, r02_lcc_heavy48_datagen90:
+  // 2.62 s -> 2.50 s)
+  if (const char* ht = getenv("GRAPEHIP_LCC_HEAVY"))
+    t.heavy_thresh = static_cast<uint32_t>(atoi(ht));
+  t.heavy_n.resize(1);
+  t.heavy_n.zero(s);
+  {
+    // worst case: every edge of the owned rows is heavy
+    uint64_t lo = 0, hi = 0;
+    HIP_CHECK(hipMemcpyAsync(&lo, goff.data() + g.v_begin, 8,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(
+        &hi, goff.data() + std::min<uint64_t>(g.v_end, nv_pad), 8,
+        hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    t.heavy_q.resize(std::max<uint64_t>(hi - lo, 1));
+  }
+  if (owned) {
+    t.wee_rows.resize(owned);
+    t.big_rows.resize(owned);
+    DeviceBuffer<unsigned long long> tcnts(2);
+    tcnts.zero(s);
+    lcc_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+        goff.data(), owned, g.v_begin, min_n, t.wee_rows.data(),
+        tcnts.data() + 0, t.big_rows.data(), tcnts.data() + 1);
+    auto tc = tcnts.download(s);
+    t.n_wee = tc[0], t.n_big = tc[1];
+  }
+  return t;
+}
+
+// the light kernels are enqueued: drop their row lists and read back how
+// many edges they deferred
+uint64_t lcc_heavy_count(LccTail& t, hipStream_t s) {
+  t.wee_rows.free();
+  t.big_rows.free();
+  unsigned long long hn = 0;
+  HIP_CHECK(hipMemcpyAsync(&hn, t.heavy_n.data(), 8, hipMemcpyDeviceToHost,
+                           s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  return hn;
+}
+
+GpuRunResult lcc_finish(const RunBracket& br, DeviceGraph& g,
+                        const LccTail& t, const DeviceBuffer<uint32_t>& Dv,
+                        double scale, bool fetch, hipStream_t s) {
+  uint32_t owned = g.owned();
+  DeviceBuffer<double> lcc_out(owned ? owned : 1);
+  if (owned)
+    lcc_finalize_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+        t.Tcnt.data(), Dv.data(), owned, g.v_begin, scale, lcc_out.data());
+  GpuRunResult res = br.finish(1, g.input_edges);
+  if (fetch) {
+    res.f64.resize(owned);
+    HIP_CHECK(hipMemcpyAsync(res.f64.data(), lcc_out.data(), owned * 8,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return res;
 }
 
 }  // namespace
@@ -6446,119 +6461,23 @@ GpuRunResult GpuContext::lcc_directed(DeviceGraph& g, bool fetch) {
 
   RunBracket br(I, comm_);
 
-  DeviceBuffer<uint32_t> Dv(nv_pad);
-  Dv.zero(s);
+  DeviceBuffer<uint32_t> Dv;
   GlobalDedupCsr U, O;
   {
-    DeviceBuffer<uint32_t> t_small(owned ? owned : 1),
-        t_mid(owned ? owned : 1), t_large(owned ? owned : 1);
-    DeviceBuffer<uint32_t> t_wavelds(owned ? owned : 1);
-    DeviceBuffer<unsigned long long> cnts(5);
-    cnts.zero(s);
-    if (owned)
-      cdlp_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-          off1, off2, owned, nullptr, cnts.data() + 3, t_small.data(),
-          cnts.data() + 0, t_wavelds.data(), cnts.data() + 4, t_mid.data(),
-          cnts.data() + 1, t_large.data(), cnts.data() + 2);
-    auto hc = cnts.download(s);
-    uint64_t n_small = hc[0], n_mid = hc[1], n_large = hc[2],
-             n_wavelds = hc[4];
-
-    DeviceBuffer<uint32_t> heavy_caps;
-    DeviceBuffer<uint64_t> heavy_off;
-    DeviceBuffer<uint32_t> tbl_lab;
-    uint64_t heavy_total = 0;
-    if (n_large) {
-      heavy_caps.resize(n_large);
-      heavy_off.resize(n_large + 1);
-      cdlp_heavy_cap_kernel<<<grid_for(n_large), kBlock, 0, s>>>(
-          off1, off2, t_large.data(), n_large, heavy_caps.data());
-      heavy_total = exclusive_scan(heavy_caps.data(), heavy_off.data(),
-                                   n_large, s, I.scan);
-      tbl_lab.resize(heavy_total);
-    }
-
-    // distinct union counts
-    if (n_small)
-      lcc_distinct_small_kernel<<<grid_for(n_small * kWave), kBlock, 0,
-                                  s>>>(off1, dst1, off2, dst2,
-                                       t_small.data(), n_small, g.v_begin,
-                                       Dv.data());
-    if (n_wavelds)
-      lcc_distinct_wave_kernel<<<grid_for(((n_wavelds + 3) / 4) * kBlock),
-                                 kBlock, 0, s>>>(off1, dst1, off2, dst2,
-                                                 t_wavelds.data(),
-                                                 n_wavelds, g.v_begin,
-                                                 Dv.data());
-    if (n_mid)
-      lcc_distinct_mid_kernel<<<std::min<int>(n_mid, kMaxGrid), kBlock, 0,
-                                s>>>(off1, dst1, off2, dst2, t_mid.data(),
-                                     n_mid, g.v_begin, Dv.data());
-    if (n_large) {
-      fill(tbl_lab.data(), kCdlpEmpty, heavy_total, s);
-      lcc_distinct_large_kernel<<<std::min<int>(n_large, kMaxGrid), kBlock,
-                                  0, s>>>(off1, dst1, off2, dst2,
-                                          t_large.data(), n_large,
-                                          heavy_off.data(), tbl_lab.data(),
-                                          g.v_begin, Dv.data());
-    }
-    if (multi) {
-      mirror_sync_begin(I, g, Dv.data(), s);
-      mirror_sync_end(I, g, Dv.data(), s);
-    }
-
-    // family builder: run the dedup pass over (o1,d1,o2,d2) with given
-    // capacities, then lift to a sparse global-index CSR (own rows, plus
-    // fetched referenced rows when lists are supplied)
-    auto build_family = [&](const uint64_t* o1, const uint32_t* d1,
-                            const uint64_t* o2, const uint32_t* d2,
-                            const DeviceBuffer<uint32_t>& caps,
-                            GlobalDedupCsr& out, bool fetch_refs) {
-      DeviceBuffer<uint64_t> ooff(owned + 1);
-      uint64_t cap_total =
-          exclusive_scan(caps.data(), ooff.data(), owned, s, I.scan);
-      DeviceBuffer<uint32_t> oadj(cap_total ? cap_total : 1);
-      DeviceBuffer<uint32_t> ocnt(owned ? owned : 1);
-      ocnt.zero(s);
-      if (n_small)
-        lcc_orient_small_kernel<<<grid_for(n_small * kWave), kBlock, 0,
-                                  s>>>(o1, d1, o2, d2, t_small.data(),
-                                       n_small, g.v_begin, Dv.data(),
-                                       ooff.data(), oadj.data(),
-                                       ocnt.data(), false);
-      if (n_mid)
-        lcc_orient_mid_kernel<<<std::min<int>(n_mid, kMaxGrid), kBlock, 0,
-                                s>>>(o1, d1, o2, d2, t_mid.data(), n_mid,
-                                     g.v_begin, Dv.data(), ooff.data(),
-                                     oadj.data(), ocnt.data(), false);
-      if (n_wavelds)
-        lcc_orient_wave_kernel<<<grid_for(((n_wavelds + 3) / 4) * kBlock),
-                                 kBlock, 0, s>>>(
-            o1, d1, o2, d2, t_wavelds.data(), n_wavelds, g.v_begin,
-            Dv.data(), ooff.data(), oadj.data(), ocnt.data(), false);
-      if (n_large) {
-        fill(tbl_lab.data(), kCdlpEmpty, heavy_total, s);
-        lcc_orient_large_kernel<<<std::min<int>(n_large, kMaxGrid), kBlock,
-                                  0, s>>>(o1, d1, o2, d2, t_large.data(),
-                                          n_large, heavy_off.data(),
-                                          tbl_lab.data(), g.v_begin,
-                                          Dv.data(), ooff.data(),
-                                          oadj.data(), ocnt.data(), false);
-      }
-      build_global_csr(I, rank_, world_, nv_pad, slice, owned, g.v_begin,
-                       ooff, ocnt, oadj, out, s,
-                       fetch_refs ? &ridx : nullptr,
-                       fetch_refs ? &roff : nullptr,
-                       fetch_refs ? &sidx : nullptr,
-                       fetch_refs ? &soff : nullptr);
-    };
+    // both families run over the tiers of the combined in+out degree
+    LccTiers tiers = build_lcc_tiers(I, off1, off2, owned, s);
+    lcc_degree_pass(I, g, tiers, off1, dst1, off2, dst2, nv_pad, multi, Dv,
+                      s);
 
     // U family: in ∪ out, cap = D — never probed remotely, stays local
     {
       DeviceBuffer<uint32_t> caps(owned ? owned : 1);
       HIP_CHECK(hipMemcpyAsync(caps.data(), Dv.data() + g.v_begin,
                                owned * 4, hipMemcpyDeviceToDevice, s));
-      build_family(off1, dst1, off2, dst2, caps, U, false);
+      build_global_csr(I, world_, nv_pad, slice, owned, g.v_begin,
+                       lcc_emit_pass(I, tiers, off1, dst1, off2, dst2, caps,
+                                     false, Dv, owned, g.v_begin, s),
+                       false, U, s);
     }
     // referenced u's = dsts of own U rows (the only rows whose O family
     // the count kernels probe)
@@ -6587,7 +6506,12 @@ GpuRunResult GpuContext::lcc_directed(DeviceGraph& g, bool fetch) {
       if (owned)
         lcc_outcap_kernel<<<grid_for(owned), kBlock, 0, s>>>(
             off1, Dv.data(), owned, g.v_begin, caps.data());
-      build_family(off1, dst1, nullptr, nullptr, caps, O, multi);
+      build_global_csr(I, world_, nv_pad, slice, owned, g.v_begin,
+                       lcc_emit_pass(I, tiers, off1, dst1, nullptr, nullptr,
+                                     caps, false, Dv, owned, g.v_begin, s),
+                       false, O, s, multi ? &ridx : nullptr,
+                       multi ? &roff : nullptr, multi ? &sidx : nullptr,
+                       multi ? &soff : nullptr);
     }
   }
 
@@ -6596,74 +6520,27 @@ GpuRunResult GpuContext::lcc_directed(DeviceGraph& g, bool fetch) {
   build_hash_sets(I, nv_pad, U, hoffU, htabU, s);
   build_hash_sets(I, nv_pad, O, hoffO, htabO, s);
 
-  DeviceBuffer<unsigned long long> Tcnt(nv_pad);
-  Tcnt.zero(s);
-  // min-side size above which an edge defers to the wave-per-edge pass;
-  // 96 -> 48 after the two-box sweep + clean full-scale re-measurement
-  // (profiles/r01_lcc_heavy_thresh_sweep.md, r02_lcc_heavy48_datagen90:
-  // 2.62 s -> 2.50 s)
-  uint32_t kHeavyThresh = 48;
-  if (const char* ht = getenv("GRAPEHIP_LCC_HEAVY"))
-    kHeavyThresh = static_cast<uint32_t>(atoi(ht));
-  DeviceBuffer<unsigned long long> heavy_q;
-  DeviceBuffer<unsigned long long> heavy_n(1);
-  heavy_n.zero(s);
-  {
-    uint64_t lo = 0, hi = 0;
-    HIP_CHECK(hipMemcpyAsync(&lo, U.goff.data() + g.v_begin, 8,
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipMemcpyAsync(&hi,
-                             U.goff.data() + std::min<uint64_t>(g.v_end,
-                                                                nv_pad),
-                             8, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    heavy_q.resize(std::max<uint64_t>(hi - lo, 1));
-  }
-  if (owned) {
-    DeviceBuffer<uint32_t> wee_rows(owned), big_rows(owned);
-    DeviceBuffer<unsigned long long> tcnts(2);
-    tcnts.zero(s);
-    lcc_dir_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        U.goff.data(), owned, g.v_begin, wee_rows.data(), tcnts.data() + 0,
-        big_rows.data(), tcnts.data() + 1);
-    auto tc = tcnts.download(s);
-    if (tc[0])
-      lcc_dir_count_wee_kernel<<<grid_for(tc[0] * kWave), kBlock, 0, s>>>(
-          U.goff.data(), U.gdst.data(), hoffU.data(), htabU.data(),
-          O.goff.data(), O.gdst.data(), hoffO.data(), htabO.data(),
-          wee_rows.data(), tc[0], g.v_begin, Tcnt.data(), kHeavyThresh,
-          heavy_q.data(), heavy_n.data());
-    if (tc[1])
-      lcc_dir_count_staged_kernel<<<std::min<uint64_t>(tc[1], kMaxGrid),
-                                    kBlock, 0, s>>>(
-          U.goff.data(), U.gdst.data(), hoffU.data(), htabU.data(),
-          O.goff.data(), O.gdst.data(), hoffO.data(), htabO.data(),
-          big_rows.data(), tc[1], g.v_begin, Tcnt.data(), kHeavyThresh,
-          heavy_q.data(), heavy_n.data());
-  }
-  {
-    unsigned long long hn = 0;
-    HIP_CHECK(hipMemcpyAsync(&hn, heavy_n.data(), 8, hipMemcpyDeviceToHost,
-                             s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (hn)
-      lcc_dir_heavy_kernel<<<grid_for(hn * kWave), kBlock, 0, s>>>(
-          U.goff.data(), U.gdst.data(), hoffU.data(), htabU.data(),
-          O.goff.data(), O.gdst.data(), hoffO.data(), htabO.data(),
-          heavy_q.data(), hn, Tcnt.data());
-  }
-  DeviceBuffer<double> lcc_out(owned ? owned : 1);
-  if (owned)
-    lcc_dir_finalize_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        Tcnt.data(), Dv.data(), owned, g.v_begin, lcc_out.data());
-  GpuRunResult res = br.finish(1, g.input_edges);
-  if (fetch) {
-    res.f64.resize(owned);
-    HIP_CHECK(hipMemcpyAsync(res.f64.data(), lcc_out.data(), owned * 8,
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  return res;
+  LccTail t = lcc_tail_begin(g, nv_pad, U.goff, 2, s);
+  if (t.n_wee)
+    lcc_dir_count_wee_kernel<<<grid_for(t.n_wee * kWave), kBlock, 0, s>>>(
+        U.goff.data(), U.gdst.data(), hoffU.data(), htabU.data(),
+        O.goff.data(), O.gdst.data(), hoffO.data(), htabO.data(),
+        t.wee_rows.data(), t.n_wee, g.v_begin, t.Tcnt.data(), t.heavy_thresh,
+        t.heavy_q.data(), t.heavy_n.data());
+  if (t.n_big)
+    lcc_dir_count_staged_kernel<<<std::min<uint64_t>(t.n_big, kMaxGrid),
+                                  kBlock, 0, s>>>(
+        U.goff.data(), U.gdst.data(), hoffU.data(), htabU.data(),
+        O.goff.data(), O.gdst.data(), hoffO.data(), htabO.data(),
+        t.big_rows.data(), t.n_big, g.v_begin, t.Tcnt.data(), t.heavy_thresh,
+        t.heavy_q.data(), t.heavy_n.data());
+  uint64_t hn = lcc_heavy_count(t, s);
+  if (hn)
+    lcc_dir_heavy_kernel<<<grid_for(hn * kWave), kBlock, 0, s>>>(
+        U.goff.data(), U.gdst.data(), hoffU.data(), htabU.data(),
+        O.goff.data(), O.gdst.data(), hoffO.data(), htabO.data(),
+        t.heavy_q.data(), hn, t.Tcnt.data());
+  return lcc_finish(br, g, t, Dv, 1.0, fetch, s);
 }
 
 GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
@@ -6678,130 +6555,33 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
 
   const uint64_t* off1 = g.oe_off.data();
   const uint32_t* dst1 = g.oe_dst.data();
-  const uint64_t* off2 = nullptr;
-  const uint32_t* dst2 = nullptr;
 
   // graph-sized working set (freed on return). Multi-GPU holds a PARTIAL
   // oriented CSR: own rows + the remote rows local oriented edges probe
   // (reference TransferAdjList staging, cuda/lcc/lcc.h:490-496, recast as
   // a one-shot referenced-row fetch) — memory and exchange volume scale
   // with the boundary, not with V.
-  uint64_t oriented_total = 0;
-  DeviceBuffer<uint32_t> Dv;                 // distinct degree, global idx
-  DeviceBuffer<uint32_t> gcnt;               // oriented count (own+referenced)
-  DeviceBuffer<uint64_t> goff;               // oriented CSR offsets (sparse)
-  DeviceBuffer<uint32_t> gdst;               // oriented CSR dsts (partial)
-  DeviceBuffer<unsigned long long> Tcnt;     // triangle credits
-  // referenced-row request lists + staging for the count sync
+  DeviceBuffer<uint32_t> Dv;  // distinct degree, global idx
+  GlobalDedupCsr O;           // oriented CSR (own + referenced rows), sorted
+  // referenced-row request lists
   DeviceBuffer<uint32_t> ridx, sidx;
   std::vector<uint64_t> roff, soff;
-  DeviceBuffer<uint8_t> rstage_s, rstage_r;
   if (multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
 
   RunBracket br(I, comm_);
 
-  // tier rows by combined degree (reuses the CDLP bucketer)
-  DeviceBuffer<uint32_t> t_small(owned), t_mid(owned), t_large(owned);
   {
-    DeviceBuffer<uint32_t> t_wavelds(owned ? owned : 1);
-    DeviceBuffer<unsigned long long> cnts(5);
-    cnts.zero(s);
-    if (owned)
-      cdlp_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-          off1, off2, owned, nullptr, cnts.data() + 3, t_small.data(),
-          cnts.data() + 0, t_wavelds.data(), cnts.data() + 4, t_mid.data(),
-          cnts.data() + 1, t_large.data(), cnts.data() + 2);
-    auto hc = cnts.download(s);
-    uint64_t n_small = hc[0], n_mid = hc[1], n_large = hc[2],
-             n_wavelds = hc[4];
+    LccTiers tiers = build_lcc_tiers(I, off1, nullptr, owned, s);
+    lcc_degree_pass(I, g, tiers, off1, dst1, nullptr, nullptr, nv_pad,
+                      multi, Dv, s);
 
-    // heavy-row hash pool (labels only)
-    DeviceBuffer<uint32_t> heavy_caps;
-    DeviceBuffer<uint64_t> heavy_off;
-    DeviceBuffer<uint32_t> tbl_lab;
-    uint64_t heavy_total = 0;
-    if (n_large) {
-      heavy_caps.resize(n_large);
-      heavy_off.resize(n_large + 1);
-      cdlp_heavy_cap_kernel<<<grid_for(n_large), kBlock, 0, s>>>(
-          off1, off2, t_large.data(), n_large, heavy_caps.data());
-      heavy_total = exclusive_scan(heavy_caps.data(), heavy_off.data(),
-                                   n_large, s, I.scan);
-      tbl_lab.resize(heavy_total);
-    }
-
-    // pass 1: distinct counts
-    Dv.resize(nv_pad);
-    Dv.zero(s);
-    if (n_small)
-      lcc_distinct_small_kernel<<<grid_for(n_small * kWave), kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, t_small.data(), n_small, g.v_begin,
-          Dv.data());
-    if (n_wavelds)
-      lcc_distinct_wave_kernel<<<grid_for(((n_wavelds + 3) / 4) * kBlock),
-                                 kBlock, 0, s>>>(off1, dst1, off2, dst2,
-                                                 t_wavelds.data(),
-                                                 n_wavelds, g.v_begin,
-                                                 Dv.data());
-    if (n_mid)
-      lcc_distinct_mid_kernel<<<std::min<int>(n_mid, kMaxGrid), kBlock, 0,
-                                s>>>(off1, dst1, off2, dst2, t_mid.data(),
-                                     n_mid, g.v_begin, Dv.data());
-    if (n_large) {
-      fill(tbl_lab.data(), kCdlpEmpty, heavy_total, s);
-      lcc_distinct_large_kernel<<<std::min<int>(n_large, kMaxGrid), kBlock, 0,
-                                  s>>>(off1, dst1, off2, dst2, t_large.data(),
-                                       n_large, heavy_off.data(),
-                                       tbl_lab.data(), g.v_begin, Dv.data());
-    }
-    if (multi) {
-      // the orient passes read Dv[dst] for local dsts only — refresh
-      // referenced entries point-to-point instead of allgathering slices
-      mirror_sync_begin(I, g, Dv.data(), s);
-      mirror_sync_end(I, g, Dv.data(), s);
-    }
-
-    // pass 2: oriented adjacency in capacity layout (cap = D per row)
+    // oriented adjacency O(v) in capacity layout (cap = D per row)
     DeviceBuffer<uint32_t> dcap(owned ? owned : 1);
     HIP_CHECK(hipMemcpyAsync(dcap.data(), Dv.data() + g.v_begin, owned * 4,
                              hipMemcpyDeviceToDevice, s));
-    DeviceBuffer<uint64_t> ooff(owned + 1);
-    uint64_t ocap_total =
-        exclusive_scan(dcap.data(), ooff.data(), owned, s, I.scan);
-    DeviceBuffer<uint32_t> oadj(ocap_total ? ocap_total : 1);
-    DeviceBuffer<uint32_t> ocnt(owned ? owned : 1);
-    ocnt.zero(s);
-    if (n_small)
-      lcc_orient_small_kernel<<<grid_for(n_small * kWave), kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, t_small.data(), n_small, g.v_begin,
-          Dv.data(), ooff.data(), oadj.data(), ocnt.data(), true);
-    if (n_mid)
-      lcc_orient_mid_kernel<<<std::min<int>(n_mid, kMaxGrid), kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, t_mid.data(), n_mid, g.v_begin, Dv.data(),
-          ooff.data(), oadj.data(), ocnt.data(), true);
-    if (n_wavelds)
-      lcc_orient_wave_kernel<<<grid_for(((n_wavelds + 3) / 4) * kBlock),
-                               kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, t_wavelds.data(), n_wavelds, g.v_begin,
-          Dv.data(), ooff.data(), oadj.data(), ocnt.data(), true);
-    if (n_large) {
-      fill(tbl_lab.data(), kCdlpEmpty, heavy_total, s);
-      lcc_orient_large_kernel<<<std::min<int>(n_large, kMaxGrid), kBlock, 0,
-                                s>>>(off1, dst1, off2, dst2, t_large.data(),
-                                     n_large, heavy_off.data(),
-                                     tbl_lab.data(), g.v_begin, Dv.data(),
-                                     ooff.data(), oadj.data(), ocnt.data(),
-                                     true);
-    }
-
-    // partial oriented CSR: own counts + counts of the rows local
-    // oriented edges reference (synced over explicit request lists so
-    // unfetched rows scan to zero length and the fetch regions stay
-    // contiguous per owner)
-    gcnt.resize(nv_pad);
-    gcnt.zero(s);
-    HIP_CHECK(hipMemcpyAsync(gcnt.data() + g.v_begin, ocnt.data(),
-                             owned * 4, hipMemcpyDeviceToDevice, s));
+    CapRows rows = lcc_emit_pass(I, tiers, off1, dst1, nullptr, nullptr,
+                                 dcap, true, Dv, owned, g.v_begin, s);
+    // request the rows local oriented edges reference
     if (multi) {
       size_t nwords = (static_cast<size_t>(nv_pad) + 31) / 32;
       DeviceBuffer<uint32_t> bm(nwords);
@@ -6810,161 +6590,49 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
         lcc_mark_oriented_kernel<<<grid_for(static_cast<size_t>(owned) *
                                             kWave),
                                    kBlock, 0, s>>>(
-            ooff.data(), ocnt.data(), oadj.data(), owned, g.v_begin,
-            g.v_end, DevBitmap{bm.data()});
-      uint64_t nref = build_ref_lists(I, comm_, bm, nwords, slice, rank_,
-                                      world_, ridx, roff, sidx, soff, s);
-      rstage_s.resize(soff[world_] * 4 + 4);
-      rstage_r.resize(nref * 4 + 4);
-      ref_sync_begin(I, sidx, soff, roff, rstage_s, rstage_r, gcnt.data(),
-                     s);
-      ref_sync_end(I, ridx, roff, rstage_r, gcnt.data(), s);
+            rows.ooff.data(), rows.ocnt.data(), rows.oadj.data(), owned,
+            g.v_begin, g.v_end, DevBitmap{bm.data()});
+      build_ref_lists(I, comm_, bm, nwords, slice, rank_, world_, ridx, roff,
+                      sidx, soff, s);
     }
-    goff.resize(static_cast<size_t>(nv_pad) + 1);
-    uint64_t g_total =
-        exclusive_scan(gcnt.data(), goff.data(), nv_pad, s, I.scan);
-    oriented_total = g_total;
-    gdst.resize(g_total ? g_total : 1);
-    if (owned)
-      lcc_compact_kernel<<<grid_for(static_cast<size_t>(owned) * kWave),
-                           kBlock, 0, s>>>(ooff.data(), ocnt.data(),
-                                           oadj.data(), goff.data(), owned,
-                                           g.v_begin, gdst.data());
-    oadj.free();
-
-    // per-row ascending sort of the owned rows
-    segmented_sort_rows(goff.data() + g.v_begin, owned,
-                        U32KeyCodec{gdst.data()}, s, I.scan);
-
-    // fetch the referenced remote rows (sorted by their owners above):
-    // each owner packs exactly the rows each peer requested; payloads
-    // land directly in the requester's contiguous per-owner gdst region
-    // (unfetched rows have zero length, so regions are hole-free)
-    if (multi) {
-      uint64_t ns = soff[world_];
-      DeviceBuffer<uint32_t> slen(ns ? ns : 1);
-      if (ns)
-        gather4_kernel<<<grid_for(ns), kBlock, 0, s>>>(
-            sidx.data(), ns, gcnt.data(), slen.data());
-      DeviceBuffer<uint64_t> spack(ns + 1);
-      uint64_t stotal =
-          exclusive_scan(slen.data(), spack.data(), ns, s, I.scan);
-      DeviceBuffer<uint32_t> srows(stotal ? stotal : 1);
-      if (ns)
-        lcc_pack_rows_kernel<<<grid_for(ns * kWave), kBlock, 0, s>>>(
-            sidx.data(), ns, goff.data(), gdst.data(), spack.data(),
-            srows.data());
-      // per-peer byte offsets: send = packed scan at list boundaries,
-      // recv = goff at slice boundaries (both derive from the same gcnt)
-      std::vector<uint64_t> sb(world_ + 1), rb(world_ + 1);
-      for (int f = 0; f <= world_; ++f) {
-        uint64_t v = 0;
-        HIP_CHECK(hipMemcpyAsync(&v, spack.data() + soff[f], 8,
-                                 hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        sb[f] = v * 4;
-        uint64_t idx = std::min<uint64_t>(
-            static_cast<uint64_t>(f) * slice, nv_pad);
-        HIP_CHECK(hipMemcpyAsync(&v, goff.data() + idx, 8,
-                                 hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipStreamSynchronize(s));
-        rb[f] = v * 4;
-      }
-      I.dc.sendrecv(reinterpret_cast<const uint8_t*>(srows.data()), sb,
-                    reinterpret_cast<uint8_t*>(gdst.data()), rb, s);
-      HIP_CHECK(hipStreamSynchronize(s));
-    }
+    // owners sort their rows before peers fetch them
+    build_global_csr(I, world_, nv_pad, slice, owned, g.v_begin,
+                     std::move(rows), true, O, s, multi ? &ridx : nullptr,
+                     multi ? &roff : nullptr, multi ? &sidx : nullptr,
+                     multi ? &soff : nullptr);
   }
 
   // per-vertex oriented hash sets (intersection via O(1) probes)
-  DeviceBuffer<uint32_t> hcap(nv_pad);
-  DeviceBuffer<uint64_t> hoff(static_cast<size_t>(nv_pad) + 1);
-  lcc_hashcap_kernel<<<grid_for(nv_pad), kBlock, 0, s>>>(goff.data(), nv_pad,
-                                                         hcap.data());
-  uint64_t htotal =
-      exclusive_scan(hcap.data(), hoff.data(), nv_pad, s, I.scan);
-  hcap.free();
-  DeviceBuffer<uint32_t> htab(htotal);
-  fill(htab.data(), kCdlpEmpty, htotal, s);
-  lcc_hashfill_kernel<<<grid_for(static_cast<size_t>(nv_pad) * kWave),
-                        kBlock, 0, s>>>(goff.data(), gdst.data(),
-                                        hoff.data(), nv_pad, htab.data());
+  DeviceBuffer<uint64_t> hoff;
+  DeviceBuffer<uint32_t> htab;
+  build_hash_sets(I, nv_pad, O, hoff, htab, s);
 
   // triangle counting: light edges inline, heavy edges deferred to a
   // wave-per-edge pass (power-law tail otherwise stalls single lanes)
-  Tcnt.resize(nv_pad);
-  Tcnt.zero(s);
-  // min-side size above which an edge defers to the wave-per-edge pass;
-  // 96 -> 48 after the two-box sweep + clean full-scale re-measurement
-  // (profiles/r01_lcc_heavy_thresh_sweep.md, r02_lcc_heavy48_datagen90:
-  // 2.62 s -> 2.50 s)
-  uint32_t kHeavyThresh = 48;
-  if (const char* ht = getenv("GRAPEHIP_LCC_HEAVY"))
-    kHeavyThresh = static_cast<uint32_t>(atoi(ht));
   const bool nowit = getenv("GRAPEHIP_LCC_NOWIT") != nullptr;
-  DeviceBuffer<unsigned long long> heavy_q;
-  DeviceBuffer<unsigned long long> heavy_n(1);
-  heavy_n.zero(s);
-  {
-    // worst case: every local oriented edge is heavy
-    uint64_t local_oedges = 0;
-    HIP_CHECK(hipMemcpyAsync(&local_oedges,
-                             goff.data() + std::min<uint64_t>(
-                                 static_cast<uint64_t>(g.v_end), nv_pad),
-                             8, hipMemcpyDeviceToHost, s));
-    uint64_t base_off = 0;
-    HIP_CHECK(hipMemcpyAsync(&base_off, goff.data() + g.v_begin, 8,
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    heavy_q.resize(std::max<uint64_t>(local_oedges - base_off, 1));
-  }
-  if (owned) {
-    DeviceBuffer<uint32_t> wee_rows(owned), big_rows(owned);
-    DeviceBuffer<unsigned long long> tcnts(2);
-    tcnts.zero(s);
-    lcc_tribucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        goff.data(), owned, g.v_begin, wee_rows.data(), tcnts.data() + 0,
-        big_rows.data(), tcnts.data() + 1);
-    auto tc = tcnts.download(s);
-    if (tc[0])
-      lcc_tri_wee_kernel<<<grid_for(tc[0] * kWave), kBlock, 0, s>>>(
-          goff.data(), gdst.data(), hoff.data(), htab.data(),
-          wee_rows.data(), tc[0], g.v_begin, Tcnt.data(), kHeavyThresh,
-          heavy_q.data(), heavy_n.data(), nowit);
-    if (tc[1])
-      lcc_tri_staged_kernel<<<std::min<uint64_t>(tc[1], kMaxGrid), kBlock,
-                              0, s>>>(
-          goff.data(), gdst.data(), hoff.data(), htab.data(),
-          big_rows.data(), tc[1], g.v_begin, Tcnt.data(), kHeavyThresh,
-          heavy_q.data(), heavy_n.data(), nowit);
-  }
-  {
-    unsigned long long hn = 0;
-    HIP_CHECK(hipMemcpyAsync(&hn, heavy_n.data(), 8, hipMemcpyDeviceToHost,
-                             s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (getenv("GRAPEHIP_DEBUG"))
-      fprintf(stderr, "[lcc] oriented_total=%llu heavy_edges=%llu\n",
-              static_cast<unsigned long long>(oriented_total),
-              static_cast<unsigned long long>(hn));
-    if (hn)
-      lcc_triangle_heavy_kernel<<<grid_for(hn * kWave), kBlock, 0, s>>>(
-          goff.data(), gdst.data(), hoff.data(), htab.data(),
-          heavy_q.data(), hn, Tcnt.data());
-  }
-  if (multi) I.dc.allreduce_sum_u64(Tcnt.data(), nv_pad, s);
-  DeviceBuffer<double> lcc_out(owned ? owned : 1);
-  if (owned)
-    lcc_finalize_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        Tcnt.data(), Dv.data(), owned, g.v_begin, lcc_out.data());
-  GpuRunResult res = br.finish(1, g.input_edges);
-  if (fetch) {
-    res.f64.resize(owned);
-    HIP_CHECK(hipMemcpyAsync(res.f64.data(), lcc_out.data(), owned * 8,
-                             hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-  }
-  return res;
+  LccTail t = lcc_tail_begin(g, nv_pad, O.goff, 1, s);
+  if (t.n_wee)
+    lcc_tri_wee_kernel<<<grid_for(t.n_wee * kWave), kBlock, 0, s>>>(
+        O.goff.data(), O.gdst.data(), hoff.data(), htab.data(),
+        t.wee_rows.data(), t.n_wee, g.v_begin, t.Tcnt.data(), t.heavy_thresh,
+        t.heavy_q.data(), t.heavy_n.data(), nowit);
+  if (t.n_big)
+    lcc_tri_staged_kernel<<<std::min<uint64_t>(t.n_big, kMaxGrid), kBlock, 0,
+                            s>>>(
+        O.goff.data(), O.gdst.data(), hoff.data(), htab.data(),
+        t.big_rows.data(), t.n_big, g.v_begin, t.Tcnt.data(), t.heavy_thresh,
+        t.heavy_q.data(), t.heavy_n.data(), nowit);
+  uint64_t hn = lcc_heavy_count(t, s);
+  if (getenv("GRAPEHIP_DEBUG"))
+    fprintf(stderr, "[lcc] oriented_total=%llu heavy_edges=%llu\n",
+            static_cast<unsigned long long>(O.total),
+            static_cast<unsigned long long>(hn));
+  if (hn)
+    lcc_triangle_heavy_kernel<<<grid_for(hn * kWave), kBlock, 0, s>>>(
+        O.goff.data(), O.gdst.data(), hoff.data(), htab.data(),
+        t.heavy_q.data(), hn, t.Tcnt.data());
+  if (multi) I.dc.allreduce_sum_u64(t.Tcnt.data(), nv_pad, s);
+  return lcc_finish(br, g, t, Dv, 2.0, fetch, s);
 }
 
 }  // namespace grapehip

@@ -16,11 +16,15 @@ ap.add_argument("--repeat", type=int, default=1,
 ap.add_argument("--warmup", type=int, default=1,
                 help="untimed runs per app first (absorbs one-time costs "
                      "like hipGraph capture, matching bench.py)")
+ap.add_argument("--directed", action="store_true",
+                help="directed graph with the in-CSR built (what the "
+                     "directed LCC needs)")
 args = ap.parse_args()
 
 eng = grapehip.Engine(rank=0, world=1, master_port=29917, gpu=True)
 g = eng.load_synthetic(num_vertices=args.nv, num_edges=args.ne, seed=42,
-                       weighted=True)
+                       weighted=True, directed=args.directed,
+                       build_in_csr=args.directed)
 def run_app(app):
     if app == "bfs":
         return eng.bfs(g, 0, values=False)
@@ -44,6 +48,8 @@ def run_app(app):
 
 
 out = {"nv": args.nv, "ne_input": args.ne, "ne_stored": g.num_edges}
+if args.directed:
+    out["directed"] = True
 for _ in range(args.warmup):
     for app in args.apps.split(","):
         run_app(app)

@@ -442,6 +442,75 @@ __global__ void scatter_edges_kernel(const uint32_t* src, const uint32_t* dst,
 }
 
 // ===========================================================================
+// Row tier partitioner, shared by the segmented sort, the pull-row buckets,
+// the CDLP/LCC degree tiers and the LCC count tiers. A classifier maps row r
+// to a bin: [0, kLists) appends r to that bin's list, [kLists, kBins) is only
+// counted, a negative value drops the row. Order inside a list is
+// unspecified.
+//
+// Block-aggregated: LDS tallies + one global reservation per block per bin
+// (405M per-thread global atomics on 3 hot words took 4.8 s).
+// ===========================================================================
+
+template <int NLISTS>
+struct TierListPtrs {
+  uint32_t* p[NLISTS];
+};
+
+template <typename Classify>
+__global__ void tier_rows_kernel(Classify cls, uint32_t rows_n,
+                                 TierListPtrs<Classify::kLists> lists,
+                                 unsigned long long* __restrict__ cnt) {
+  constexpr int NBINS = Classify::kBins, NLISTS = Classify::kLists;
+  __shared__ uint32_t s_cnt[NBINS];
+  __shared__ unsigned long long s_base[NLISTS];
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t base = blockIdx.x * blockDim.x; base < rows_n;
+       base += stride) {
+    if (threadIdx.x < NBINS) s_cnt[threadIdx.x] = 0;
+    __syncthreads();
+    uint32_t r = base + threadIdx.x;
+    int b = -1;
+    uint32_t loc = 0;
+    if (r < rows_n) {
+      b = cls(r);
+      if (b >= 0) loc = atomicAdd(&s_cnt[b], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < NBINS && s_cnt[threadIdx.x]) {
+      unsigned long long at =
+          atomicAdd(cnt + threadIdx.x,
+                    static_cast<unsigned long long>(s_cnt[threadIdx.x]));
+      if (threadIdx.x < NLISTS) s_base[threadIdx.x] = at;
+    }
+    __syncthreads();
+    if (b >= 0 && b < NLISTS) lists.p[b][s_base[b] + loc] = r;
+    __syncthreads();
+  }
+}
+
+// Partitions rows [0, rows_n) on stream s: sizes every non-null list for
+// rows_n entries, launches, and reads the kBins counts back (one sync of s).
+// A null list is for a bin the classifier never returns.
+template <typename Classify>
+std::vector<unsigned long long> partition_rows(
+    Classify cls, uint32_t rows_n,
+    DeviceBuffer<uint32_t>* const (&lists)[Classify::kLists],
+    hipStream_t s) {
+  TierListPtrs<Classify::kLists> ptrs;
+  for (int b = 0; b < Classify::kLists; ++b) {
+    if (lists[b]) lists[b]->resize(rows_n ? rows_n : 1);
+    ptrs.p[b] = lists[b] ? lists[b]->data() : nullptr;
+  }
+  DeviceBuffer<unsigned long long> cnts(Classify::kBins);
+  cnts.zero(s);
+  if (rows_n)
+    tier_rows_kernel<<<grid_for(rows_n), kBlock, 0, s>>>(cls, rows_n, ptrs,
+                                                         cnts.data());
+  return cnts.download(s);
+}
+
+// ===========================================================================
 // Segmented sort (ascending keys per CSR row), shared by the adjacency sort
 // of a freshly built device CSR and by LCC's oriented CSR. Ascending
 // neighbor ids turn the pull kernels' random gathers into locally-increasing
@@ -496,43 +565,16 @@ __device__ __forceinline__ void bitonic_stage(Key* a, uint32_t n, uint32_t k,
   }
 }
 
-// bucket rows for the sort tiers by length (block-aggregated counter
-// reservation, same pattern as bucket_rows_kernel); rows of 0 or 1 keys
-// are in no bucket
-__global__ void seg_sortbucket_kernel(const uint64_t* __restrict__ off,
-                                      uint32_t rows_n, uint32_t* lds_rows,
-                                      unsigned long long* c_lds,
-                                      uint32_t* big_rows,
-                                      unsigned long long* c_big) {
-  __shared__ uint32_t s_cnt[2];
-  __shared__ unsigned long long s_base[2];
-  uint32_t* lists[2] = {lds_rows, big_rows};
-  unsigned long long* gcnt[2] = {c_lds, c_big};
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < rows_n;
-       base += stride) {
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t r = base + threadIdx.x;
-    int b = -1;
-    uint32_t loc = 0;
-    if (r < rows_n) {
-      uint64_t n = off[r + 1] - off[r];
-      if (n >= 2) {
-        b = n <= kSegSortLds ? 0 : 1;
-        loc = atomicAdd(&s_cnt[b], 1u);
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x])
-      s_base[threadIdx.x] =
-          atomicAdd(gcnt[threadIdx.x],
-                    static_cast<unsigned long long>(s_cnt[threadIdx.x]));
-    __syncthreads();
-    if (b >= 0) lists[b][s_base[b] + loc] = r;
-    __syncthreads();
+// sort tiers by row length: LDS bitonic, global-scratch bitonic; rows of 0 or
+// 1 keys need no sort and are in no tier
+struct SortLenTiers {
+  static constexpr int kLists = 2, kBins = 2;
+  const uint64_t* __restrict__ off;
+  __device__ __forceinline__ int operator()(uint32_t r) const {
+    uint64_t n = off[r + 1] - off[r];
+    return n < 2 ? -1 : (n <= kSegSortLds ? 0 : 1);
   }
-}
+};
 
 template <typename Codec>
 __global__ void seg_sort_lds_kernel(const uint64_t* __restrict__ off,
@@ -1666,56 +1708,28 @@ namespace grapehip {
 constexpr uint64_t kSmallDeg = 64;
 constexpr uint64_t kMidDeg = 16384;
 
-// Block-aggregated: LDS tallies + one global reservation per block per
-// bucket (405M per-thread global atomics on 3 hot words took 4.8 s).
-//
-// Rows with no pull edge go into no list. Those that have no out-edge
-// either (out_off == off for undirected graphs) are isolated and only
-// counted: cnt[3] for real rows, cnt[4] for padding rows >= owned_real.
-// cnt[0..2] are the small/mid/large list lengths.
 __device__ __forceinline__ bool row_has_edges(
     const uint64_t* __restrict__ off, const uint64_t* __restrict__ out_off,
     uint32_t r) {
   return off[r + 1] != off[r] || out_off[r + 1] != out_off[r];
 }
 
-__global__ void bucket_rows_kernel(const uint64_t* __restrict__ off,
-                                   const uint64_t* __restrict__ out_off,
-                                   uint32_t owned, uint32_t owned_real,
-                                   uint32_t* sm, uint32_t* md, uint32_t* lg,
-                                   unsigned long long* cnt) {
-  __shared__ uint32_t s_cnt[5];
-  __shared__ unsigned long long s_base[3];
-  uint32_t* lists[3] = {sm, md, lg};
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < owned;
-       base += stride) {
-    if (threadIdx.x < 5) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t r = base + threadIdx.x;
-    int b = -1;
-    uint32_t loc = 0;
-    if (r < owned) {
-      uint64_t deg = off[r + 1] - off[r];
-      if (deg) {
-        b = deg < kSmallDeg ? 0 : (deg < kMidDeg ? 1 : 2);
-        loc = atomicAdd(&s_cnt[b], 1u);
-      } else if (out_off[r + 1] == out_off[r]) {
-        atomicAdd(&s_cnt[r < owned_real ? 3 : 4], 1u);
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 5 && s_cnt[threadIdx.x]) {
-      unsigned long long at =
-          atomicAdd(cnt + threadIdx.x,
-                    static_cast<unsigned long long>(s_cnt[threadIdx.x]));
-      if (threadIdx.x < 3) s_base[threadIdx.x] = at;
-    }
-    __syncthreads();
-    if (b >= 0) lists[b][s_base[b] + loc] = r;
-    __syncthreads();
+// Pull-degree tiers (lists small/mid/large). Rows with no pull edge go into
+// no list. Those that have no out-edge either (out_off == off for undirected
+// graphs) are isolated and only counted: bin 3 for real rows, bin 4 for
+// padding rows >= owned_real.
+struct PullDegTiers {
+  static constexpr int kLists = 3, kBins = 5;
+  const uint64_t* __restrict__ off;
+  const uint64_t* __restrict__ out_off;
+  uint32_t owned_real;
+  __device__ __forceinline__ int operator()(uint32_t r) const {
+    uint64_t deg = off[r + 1] - off[r];
+    if (deg) return deg < kSmallDeg ? 0 : (deg < kMidDeg ? 1 : 2);
+    if (out_off[r + 1] == out_off[r]) return r < owned_real ? 3 : 4;
+    return -1;
   }
-}
+};
 
 // One bitmap word per thread: bit r%32 of word r/32 is set when owned row r
 // has an edge. No atomics; compacted into rows_active (ascending).
@@ -2558,15 +2572,9 @@ template <typename Codec>
 void segmented_sort_rows(const uint64_t* off, uint32_t rows_n, Codec codec,
                          hipStream_t s, ScanTemp& scan) {
   using Key = typename Codec::Key;
-  DeviceBuffer<uint32_t> lds_rows(rows_n ? rows_n : 1),
-      big_rows(rows_n ? rows_n : 1);
-  DeviceBuffer<unsigned long long> cnts(2);
-  cnts.zero(s);
-  if (rows_n)
-    seg_sortbucket_kernel<<<grid_for(rows_n), kBlock, 0, s>>>(
-        off, rows_n, lds_rows.data(), cnts.data() + 0, big_rows.data(),
-        cnts.data() + 1);
-  auto h = cnts.download(s);
+  DeviceBuffer<uint32_t> lds_rows, big_rows;
+  auto h = partition_rows(SortLenTiers{off}, rows_n, {&lds_rows, &big_rows},
+                          s);
   const uint64_t n_lds = h[0], n_big = h[1];
   if (n_lds)
     seg_sort_lds_kernel<<<std::min<uint64_t>(n_lds, kMaxGrid), kBlock, 0,
@@ -3108,15 +3116,9 @@ static void ensure_buckets(DeviceGraph& g, GpuContext::Impl& I,
   uint32_t owned = g.owned();
   const uint64_t* pull_off = !g.directed ? g.oe_off.data() : g.ie_off.data();
   const uint64_t* out_off = g.oe_off.data();
-  g.rows_small.resize(owned);
-  g.rows_mid.resize(owned);
-  g.rows_large.resize(owned);
-  DeviceBuffer<unsigned long long> cnts(5);
-  cnts.zero(s);
-  bucket_rows_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-      pull_off, out_off, owned, g.owned_real, g.rows_small.data(),
-      g.rows_mid.data(), g.rows_large.data(), cnts.data());
-  auto h = cnts.download(s);
+  auto h = partition_rows(PullDegTiers{pull_off, out_off, g.owned_real},
+                          owned, {&g.rows_small, &g.rows_mid, &g.rows_large},
+                          s);
   g.n_small = h[0];
   g.n_mid = h[1];
   g.n_large = h[2];
@@ -4527,27 +4529,34 @@ GpuRunResult GpuContext::wcc(DeviceGraph& g, bool fetch) {
 // cuda/cdlp/cdlp.h). MI355X design: instead of the reference's CUB segmented
 // radix sort per adjacency (cuda/cdlp/cdlp.h:199-251), the label mode is
 // computed with degree-tiered counting:
+//   * deg <= 16:      thread-per-row, labels in registers
 //   * deg <= 64:      wave-per-row ballot mode (no memory traffic at all —
 //                     the wave votes labels off with __ballot/popcount)
+//   * deg <= 512:     wave-per-row open-addressing hash in LDS, 4 rows per
+//                     block (1024 slots x (label,count) each)
 //   * deg <= 4096:    block-per-row open-addressing hash in LDS (64 KB:
 //                     8192 slots x (label,count)), LDS atomics
 //   * heavier rows:   block-per-row global-memory hash (L2 atomics), table
 //                     space carved from one scratch pool by prefix sum
+// The tiers come from the shared row partitioner; LCC's neighbor dedup runs
+// over the same tiers (minus the first) with the same row decoder.
 // Labels are u32 global vids (identity oids); each iteration refreshes the
 // replicated label array with an in-place ncclAllGather over xGMI (the
 // dense analogue of the reference's SendMsgThroughOEdges label push).
 // Directed graphs use the in+out multiset (both CSRs), like the CPU app.
 // ---------------------------------------------------------------------------
 
-constexpr uint32_t kCdlpTinyDeg = 16;      // thread-per-row register tier
-constexpr uint32_t kCdlpSmallDeg = 64;     // wave-ballot tier bound
-constexpr uint32_t kCdlpWaveSlots = 1024;  // wave-hash tier (4 rows/block)
-constexpr uint32_t kCdlpWaveDeg = kCdlpWaveSlots / 2;
-constexpr uint32_t kCdlpLdsSlots = 8192;   // 64 KB LDS table (mid tier)
-constexpr uint32_t kCdlpMidDeg = kCdlpLdsSlots / 2;  // load factor <= 0.5
-constexpr uint32_t kCdlpEmpty = 0xFFFFFFFFu;
+// --- pieces shared with LCC's dedup tiers: bounds, row decoder, hash -------
 
-__device__ __forceinline__ uint32_t cdlp_hash(uint32_t x) {
+constexpr uint32_t kTierTinyDeg = 16;      // thread-per-row register tier
+constexpr uint32_t kTierSmallDeg = 64;     // wave-ballot tier bound
+constexpr uint32_t kTierWaveSlots = 1024;  // wave-hash tier (4 rows/block)
+constexpr uint32_t kTierWaveDeg = kTierWaveSlots / 2;
+constexpr uint32_t kTierMidSlots = 8192;   // block-per-row LDS table
+constexpr uint32_t kTierMidDeg = kTierMidSlots / 2;  // load factor <= 0.5
+constexpr uint32_t kSlotEmpty = 0xFFFFFFFFu;
+
+__device__ __forceinline__ uint32_t slot_hash(uint32_t x) {
   x ^= x >> 16;
   x *= 0x7feb352du;
   x ^= x >> 15;
@@ -4556,57 +4565,154 @@ __device__ __forceinline__ uint32_t cdlp_hash(uint32_t x) {
   return x;
 }
 
-// combined-degree bucketing over (out [+ in]) adjacency.
-// tiny rows get thread-per-row register-mode treatment (tn nullptr folds
-// them into the small/wave tier — the LCC reuse keeps three tiers).
-__global__ void cdlp_bucket_kernel(const uint64_t* __restrict__ off1,
-                                   const uint64_t* __restrict__ off2,
-                                   uint32_t owned, uint32_t* tn,
-                                   unsigned long long* ct, uint32_t* sm,
-                                   unsigned long long* cs, uint32_t* wv,
-                                   unsigned long long* cw, uint32_t* md,
-                                   unsigned long long* cm, uint32_t* lg,
-                                   unsigned long long* cl) {
-  __shared__ uint32_t s_cnt[5];
-  __shared__ unsigned long long s_base[5];
-  uint32_t* lists[5] = {tn, sm, wv, md, lg};
-  unsigned long long* gcnt[5] = {ct, cs, cw, cm, cl};
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < owned;
-       base += stride) {
-    if (threadIdx.x < 5) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t r = base + threadIdx.x;
-    int b = -1;
-    uint32_t loc = 0;
-    if (r < owned) {
-      uint64_t deg = off1[r + 1] - off1[r];
-      if (off2) deg += off2[r + 1] - off2[r];
-      if (tn && deg <= kCdlpTinyDeg)
-        b = 0;
-      else if (deg <= kCdlpSmallDeg)
-        b = 1;
-      else if (wv && deg <= kCdlpWaveDeg)
-        b = 2;
-      else if (deg <= kCdlpMidDeg)
-        b = 3;
-      else
-        b = 4;
-      loc = atomicAdd(&s_cnt[b], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x < 5 && s_cnt[threadIdx.x])
-      s_base[threadIdx.x] =
-          atomicAdd(gcnt[threadIdx.x],
-                    static_cast<unsigned long long>(s_cnt[threadIdx.x]));
-    __syncthreads();
-    if (b >= 0) lists[b][s_base[b] + loc] = r;
-    __syncthreads();
+// row r of the combined (off1 [+ off2]) adjacency, decoded; Len is u32
+// except in the large tier
+template <typename Len>
+struct AdjRow {
+  uint32_t v;
+  uint64_t b1, b2;
+  Len d1, deg;
+  __device__ __forceinline__ uint32_t at(const uint32_t* __restrict__ dst1,
+                                         const uint32_t* __restrict__ dst2,
+                                         Len k) const {
+    return k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
+  }
+};
+
+template <typename Len>
+__device__ __forceinline__ AdjRow<Len> adj_row(
+    const uint64_t* __restrict__ off1, const uint64_t* __restrict__ off2,
+    uint32_t r, uint32_t v_begin) {
+  AdjRow<Len> row;
+  row.v = v_begin + r;
+  row.b1 = off1[r];
+  row.d1 = static_cast<Len>(off1[r + 1] - row.b1);
+  row.deg = row.d1;
+  row.b2 = 0;
+  if (off2) {
+    row.b2 = off2[r];
+    row.deg += static_cast<Len>(off2[r + 1] - row.b2);
+  }
+  return row;
+}
+
+// LDS table size for a row: pow2 >= 2*deg, clamped to the tier's slots
+__device__ __forceinline__ uint32_t lds_table_cap(uint32_t deg,
+                                                  uint32_t slots) {
+  uint32_t cap = 64;
+  while (cap < 2 * deg) cap <<= 1;
+  return cap > slots ? slots : cap;
+}
+
+// Tiers by combined degree, lists in degree order: tiny, small, wave, mid,
+// large. The tiny tier is CDLP's; without it those rows are small rows.
+struct CombinedDegTiers {
+  static constexpr int kLists = 5, kBins = 5;
+  const uint64_t* __restrict__ off1;
+  const uint64_t* __restrict__ off2;
+  bool tiny;
+  __device__ __forceinline__ int operator()(uint32_t r) const {
+    uint64_t deg = adj_row<uint64_t>(off1, off2, r, 0).deg;
+    if (deg <= kTierSmallDeg) return tiny && deg <= kTierTinyDeg ? 0 : 1;
+    return deg <= kTierWaveDeg ? 2 : (deg <= kTierMidDeg ? 3 : 4);
+  }
+};
+
+// per-large-row global table capacity (pow2 >= 2*deg)
+__global__ void heavy_cap_kernel(const uint64_t* __restrict__ off1,
+                                 const uint64_t* __restrict__ off2,
+                                 const uint32_t* __restrict__ rows,
+                                 uint64_t nrows, uint32_t* __restrict__ caps) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < nrows; i += stride) {
+    uint64_t deg = adj_row<uint64_t>(off1, off2, rows[i], 0).deg;
+    uint64_t cap = 1024;
+    while (cap < 2 * deg) cap <<= 1;
+    caps[i] = static_cast<uint32_t>(cap);
   }
 }
 
-// thread-per-row register mode for deg <= 8 (most power-law rows):
-// a wave-per-row ballot on a deg-3 row idles 61 lanes
+// --- CDLP's own pieces ------------------------------------------------------
+
+// a null bitmap means every row is dirty
+__device__ __forceinline__ bool row_is_dirty(
+    const uint32_t* __restrict__ dirty, uint32_t v) {
+  return !dirty || ((dirty[v >> 5] >> (v & 31)) & 1);
+}
+
+// Mode key: higher count wins, then the lower label. 0 is "no label seen".
+__device__ __forceinline__ uint64_t mode_key(uint32_t cnt, uint32_t label) {
+  return (static_cast<uint64_t>(cnt) << 32) | static_cast<uint32_t>(~label);
+}
+__device__ __forceinline__ uint32_t mode_label(uint64_t key) {
+  return ~static_cast<uint32_t>(key);
+}
+
+__device__ __forceinline__ uint64_t wave_max(uint64_t key) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    uint64_t o = __shfl_down(static_cast<unsigned long long>(key), d, 64);
+    if (o > key) key = o;
+  }
+  return key;  // lane 0 holds the maximum
+}
+
+// block argmax of mode keys; an empty row (no key) keeps `own`
+__device__ __forceinline__ void cdlp_block_argmax(uint64_t key,
+                                                  uint32_t* out,
+                                                  uint32_t own) {
+  __shared__ uint64_t s_wave[kBlock / kWave];
+  key = wave_max(key);
+  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = key;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint64_t best = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / kWave; ++w)
+      if (s_wave[w] > best) best = s_wave[w];
+    *out = best ? mode_label(best) : own;
+  }
+  __syncthreads();
+}
+
+// LDS open-addressing (label, count) table of the wave and mid tiers
+__device__ __forceinline__ void lds_count_insert(uint32_t* s_lab,
+                                                 uint32_t* s_cnt,
+                                                 uint32_t mask, uint32_t l) {
+  uint32_t idx = slot_hash(l) & mask;
+  for (;;) {
+    uint32_t old = atomicCAS(&s_lab[idx], kSlotEmpty, l);
+    if (old == kSlotEmpty || old == l) {
+      atomicAdd(&s_cnt[idx], 1u);
+      return;
+    }
+    idx = (idx + 1) & mask;
+  }
+}
+
+// this thread's best key over slots first, first + step, ... of the table
+__device__ __forceinline__ uint64_t lds_table_mode(const uint32_t* s_lab,
+                                                   const uint32_t* s_cnt,
+                                                   uint32_t cap,
+                                                   uint32_t first,
+                                                   uint32_t step) {
+  uint64_t key = 0;
+  for (uint32_t k = first; k < cap; k += step) {
+    uint32_t c = s_cnt[k];
+    if (c) {
+      uint64_t cand = mode_key(c, s_lab[k]);
+      if (cand > key) key = cand;
+    }
+  }
+  return key;
+}
+
+// In every tier a row of degree 0 keeps its own label.
+
+// thread-per-row register mode for deg <= kTierTinyDeg (most power-law
+// rows): a wave-per-row ballot on a deg-3 row idles 61 lanes
 __global__ void cdlp_tiny_kernel(const uint64_t* __restrict__ off1,
                                  const uint32_t* __restrict__ dst1,
                                  const uint64_t* __restrict__ off2,
@@ -4621,35 +4727,24 @@ __global__ void cdlp_tiny_kernel(const uint64_t* __restrict__ off1,
                     threadIdx.x;
        i < nrows; i += stride) {
     uint32_t r = rows[i];
-    if (dirty) {
-      uint32_t vg = v_begin + r;
-      if (!((dirty[vg >> 5] >> (vg & 31)) & 1)) continue;
-    }
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint32_t d1 = static_cast<uint32_t>(e1 - b1);
-    uint32_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += static_cast<uint32_t>(off2[r + 1] - b2);
-    }
-    if (deg == 0) {
-      next[r] = lab[v_begin + r];
+    if (!row_is_dirty(dirty, v_begin + r)) continue;
+    AdjRow<uint32_t> row = adj_row<uint32_t>(off1, off2, r, v_begin);
+    if (row.deg == 0) {
+      next[r] = lab[row.v];
       continue;
     }
-    uint32_t l[kCdlpTinyDeg];
+    uint32_t l[kTierTinyDeg];
 #pragma unroll
-    for (uint32_t k = 0; k < kCdlpTinyDeg; ++k)
-      if (k < deg)
-        l[k] = k < d1 ? lab[dst1[b1 + k]] : lab[dst2[b2 + (k - d1)]];
-    uint32_t best_lab = kCdlpEmpty, best_cnt = 0;
-    for (uint32_t k = 0; k < deg; ++k) {
+    for (uint32_t k = 0; k < kTierTinyDeg; ++k)
+      if (k < row.deg) l[k] = lab[row.at(dst1, dst2, k)];
+    uint32_t best_lab = kSlotEmpty, best_cnt = 0;
+    for (uint32_t k = 0; k < row.deg; ++k) {
       bool first = true;
       for (uint32_t j = 0; j < k; ++j)
         if (l[j] == l[k]) first = false;
       if (!first) continue;
       uint32_t cnt = 1;
-      for (uint32_t j = k + 1; j < deg; ++j)
+      for (uint32_t j = k + 1; j < row.deg; ++j)
         if (l[j] == l[k]) ++cnt;
       if (cnt > best_cnt || (cnt == best_cnt && l[k] < best_lab)) {
         best_cnt = cnt;
@@ -4660,7 +4755,7 @@ __global__ void cdlp_tiny_kernel(const uint64_t* __restrict__ off1,
   }
 }
 
-// wave-per-row ballot mode, deg <= 64
+// wave-per-row ballot mode, deg <= kTierSmallDeg (one lane per arc)
 __global__ void cdlp_small_kernel(const uint64_t* __restrict__ off1,
                                   const uint32_t* __restrict__ dst1,
                                   const uint64_t* __restrict__ off2,
@@ -4670,38 +4765,25 @@ __global__ void cdlp_small_kernel(const uint64_t* __restrict__ off1,
                                   uint64_t nrows, uint32_t v_begin,
                                   const uint32_t* __restrict__ dirty,
                                   uint32_t* __restrict__ next) {
-  const int lane = threadIdx.x & 63;
+  const uint32_t lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   const int wpb = kBlock / kWave;
   size_t wstride = static_cast<size_t>(gridDim.x) * wpb;
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * wpb + wid; i < nrows;
        i += wstride) {
     uint32_t r = rows[i];
-    if (dirty) {
-      uint32_t v = v_begin + r;
-      if (!((dirty[v >> 5] >> (v & 31)) & 1)) continue;
-    }
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint32_t d1 = static_cast<uint32_t>(e1 - b1);
-    uint32_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += static_cast<uint32_t>(off2[r + 1] - b2);
-    }
-    if (deg == 0) {
-      if (lane == 0) next[r] = lab[v_begin + r];
+    if (!row_is_dirty(dirty, v_begin + r)) continue;
+    AdjRow<uint32_t> row = adj_row<uint32_t>(off1, off2, r, v_begin);
+    if (row.deg == 0) {
+      if (lane == 0) next[r] = lab[row.v];
       continue;
     }
-    uint32_t mylab = kCdlpEmpty;
-    if (lane < static_cast<int>(deg))
-      mylab = lane < static_cast<int>(d1)
-                  ? lab[dst1[b1 + lane]]
-                  : lab[dst2[b2 + (lane - d1)]];
-    unsigned long long remaining = __ballot(lane < static_cast<int>(deg));
-    uint32_t best_cnt = 0, best_lab = kCdlpEmpty;
+    uint32_t mylab = kSlotEmpty;
+    if (lane < row.deg) mylab = lab[row.at(dst1, dst2, lane)];
+    unsigned long long remaining = __ballot(lane < row.deg);
+    uint32_t best_cnt = 0, best_lab = kSlotEmpty;
     while (remaining) {
-      int L = __ffsll(static_cast<unsigned long long>(remaining)) - 1;
+      int L = __ffsll(remaining) - 1;
       uint32_t lab0 = __shfl(mylab, L, 64);
       unsigned long long m = __ballot(mylab == lab0) & remaining;
       remaining &= ~m;
@@ -4715,31 +4797,9 @@ __global__ void cdlp_small_kernel(const uint64_t* __restrict__ off1,
   }
 }
 
-// shared argmax reduce over (count, ~label) keys
-__device__ __forceinline__ void cdlp_block_argmax(uint64_t key,
-                                                  uint32_t* out,
-                                                  uint32_t fallback) {
-  __shared__ uint64_t s_wave[kBlock / kWave];
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    uint64_t o = __shfl_down(static_cast<unsigned long long>(key), d, 64);
-    if (o > key) key = o;
-  }
-  if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = key;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint64_t best = 0;
-#pragma unroll
-    for (int w = 0; w < kBlock / kWave; ++w)
-      if (s_wave[w] > best) best = s_wave[w];
-    *out = best ? ~static_cast<uint32_t>(best) : fallback;
-  }
-  __syncthreads();
-}
-
-// 4-rows-per-block wave hash for 64 < deg <= kCdlpWaveDeg: a block-per-row
-// table on a deg-100 row leaves 3 of 4 waves idle; here each wave owns a
-// 1024-slot LDS region and the group loop is uniform so plain
+// 4-rows-per-block wave hash for kTierSmallDeg < deg <= kTierWaveDeg: a
+// block-per-row table on a deg-100 row leaves 3 of 4 waves idle; here each
+// wave owns a 1024-slot LDS region and the group loop is uniform so plain
 // __syncthreads stages the clear/insert/reduce phases.
 __global__ void cdlp_wave_kernel(const uint64_t* __restrict__ off1,
                                  const uint32_t* __restrict__ dst1,
@@ -4750,8 +4810,8 @@ __global__ void cdlp_wave_kernel(const uint64_t* __restrict__ off1,
                                  uint64_t nrows, uint32_t v_begin,
                                  const uint32_t* __restrict__ dirty,
                                  uint32_t* __restrict__ next) {
-  __shared__ uint32_t s_lab[4][kCdlpWaveSlots];
-  __shared__ uint32_t s_cnt[4][kCdlpWaveSlots];
+  __shared__ uint32_t s_lab[4][kTierWaveSlots];
+  __shared__ uint32_t s_cnt[4][kTierWaveSlots];
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
   uint64_t groups = (nrows + 3) / 4;
@@ -4759,70 +4819,34 @@ __global__ void cdlp_wave_kernel(const uint64_t* __restrict__ off1,
     uint64_t i = grp * 4 + wid;
     bool have = i < nrows;
     uint32_t r = have ? rows[i] : 0;
-    if (have && dirty) {
-      uint32_t vg = v_begin + r;
-      if (!((dirty[vg >> 5] >> (vg & 31)) & 1)) have = false;
-    }
-    uint32_t d1 = 0, deg = 0;
-    uint64_t b1 = 0, b2 = 0;
-    uint32_t cap = 64, mask = 63;
+    if (have && !row_is_dirty(dirty, v_begin + r)) have = false;
+    AdjRow<uint32_t> row{};
+    uint32_t cap = 64;
     if (have) {
-      b1 = off1[r];
-      d1 = static_cast<uint32_t>(off1[r + 1] - b1);
-      deg = d1;
-      if (off2) {
-        b2 = off2[r];
-        deg += static_cast<uint32_t>(off2[r + 1] - b2);
-      }
-      while (cap < 2 * deg) cap <<= 1;
-      if (cap > kCdlpWaveSlots) cap = kCdlpWaveSlots;
-      mask = cap - 1;
+      row = adj_row<uint32_t>(off1, off2, r, v_begin);
+      cap = lds_table_cap(row.deg, kTierWaveSlots);
       for (uint32_t k = lane; k < cap; k += kWave) {
-        s_lab[wid][k] = kCdlpEmpty;
+        s_lab[wid][k] = kSlotEmpty;
         s_cnt[wid][k] = 0;
       }
     }
     __syncthreads();
-    if (have) {
-      for (uint32_t k = lane; k < deg; k += kWave) {
-        uint32_t l = k < d1 ? lab[dst1[b1 + k]] : lab[dst2[b2 + (k - d1)]];
-        uint32_t idx = cdlp_hash(l) & mask;
-        for (;;) {
-          uint32_t old = atomicCAS(&s_lab[wid][idx], kCdlpEmpty, l);
-          if (old == kCdlpEmpty || old == l) {
-            atomicAdd(&s_cnt[wid][idx], 1u);
-            break;
-          }
-          idx = (idx + 1) & mask;
-        }
-      }
-    }
+    if (have)
+      for (uint32_t k = lane; k < row.deg; k += kWave)
+        lds_count_insert(s_lab[wid], s_cnt[wid], cap - 1,
+                         lab[row.at(dst1, dst2, k)]);
     __syncthreads();
     if (have) {
-      uint64_t key = 0;
-      for (uint32_t k = lane; k < cap; k += kWave) {
-        uint32_t c = s_cnt[wid][k];
-        if (c) {
-          uint64_t cand = (static_cast<uint64_t>(c) << 32) |
-                          static_cast<uint32_t>(~s_lab[wid][k]);
-          if (cand > key) key = cand;
-        }
-      }
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) {
-        uint64_t o = __shfl_down(static_cast<unsigned long long>(key), d,
-                                 64);
-        if (o > key) key = o;
-      }
-      if (lane == 0)
-        next[r] = key ? ~static_cast<uint32_t>(key)
-                      : (deg ? 0 : lab[v_begin + r]);
+      uint64_t key =
+          wave_max(lds_table_mode(s_lab[wid], s_cnt[wid], cap, lane, kWave));
+      // no key: the row is empty (a row with arcs always counts a label)
+      if (lane == 0) next[r] = key ? mode_label(key) : lab[row.v];
     }
     __syncthreads();
   }
 }
 
-// block-per-row LDS hash, deg <= kCdlpMidDeg
+// block-per-row LDS hash, kTierWaveDeg < deg <= kTierMidDeg
 __global__ void cdlp_mid_kernel(const uint64_t* __restrict__ off1,
                                 const uint32_t* __restrict__ dst1,
                                 const uint64_t* __restrict__ off2,
@@ -4832,80 +4856,34 @@ __global__ void cdlp_mid_kernel(const uint64_t* __restrict__ off1,
                                 uint64_t nrows, uint32_t v_begin,
                                 const uint32_t* __restrict__ dirty,
                                 uint32_t* __restrict__ next) {
-  __shared__ uint32_t s_lab[kCdlpLdsSlots];
-  __shared__ uint32_t s_cnt[kCdlpLdsSlots];
+  __shared__ uint32_t s_lab[kTierMidSlots];
+  __shared__ uint32_t s_cnt[kTierMidSlots];
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
-    if (dirty) {
-      uint32_t vg = v_begin + r;
-      if (!((dirty[vg >> 5] >> (vg & 31)) & 1)) continue;
-    }
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint32_t d1 = static_cast<uint32_t>(e1 - b1);
-    uint32_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += static_cast<uint32_t>(off2[r + 1] - b2);
-    }
-    // capacity: pow2 >= 2*deg, <= kCdlpLdsSlots
-    uint32_t cap = 64;
-    while (cap < 2 * deg) cap <<= 1;
-    if (cap > kCdlpLdsSlots) cap = kCdlpLdsSlots;
-    const uint32_t mask = cap - 1;
+    if (!row_is_dirty(dirty, v_begin + r)) continue;
+    AdjRow<uint32_t> row = adj_row<uint32_t>(off1, off2, r, v_begin);
+    const uint32_t cap = lds_table_cap(row.deg, kTierMidSlots);
     for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x) {
-      s_lab[k] = kCdlpEmpty;
+      s_lab[k] = kSlotEmpty;
       s_cnt[k] = 0;
     }
     __syncthreads();
-    for (uint32_t k = threadIdx.x; k < deg; k += blockDim.x) {
-      uint32_t l = k < d1 ? lab[dst1[b1 + k]] : lab[dst2[b2 + (k - d1)]];
-      uint32_t idx = cdlp_hash(l) & mask;
-      for (;;) {
-        uint32_t old = atomicCAS(&s_lab[idx], kCdlpEmpty, l);
-        if (old == kCdlpEmpty || old == l) {
-          atomicAdd(&s_cnt[idx], 1u);
-          break;
-        }
-        idx = (idx + 1) & mask;
-      }
-    }
+    for (uint32_t k = threadIdx.x; k < row.deg; k += blockDim.x)
+      lds_count_insert(s_lab, s_cnt, cap - 1, lab[row.at(dst1, dst2, k)]);
     __syncthreads();
-    uint64_t key = 0;
-    for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x) {
-      uint32_t c = s_cnt[k];
-      if (c) {
-        uint64_t cand = (static_cast<uint64_t>(c) << 32) |
-                        static_cast<uint32_t>(~s_lab[k]);
-        if (cand > key) key = cand;
-      }
-    }
-    cdlp_block_argmax(key, &next[r], lab[v_begin + r]);
+    cdlp_block_argmax(
+        lds_table_mode(s_lab, s_cnt, cap, threadIdx.x, blockDim.x), &next[r],
+        lab[row.v]);
   }
 }
 
-// per-heavy-row table capacity (pow2 >= 2*deg)
-__global__ void cdlp_heavy_cap_kernel(const uint64_t* __restrict__ off1,
-                                      const uint64_t* __restrict__ off2,
-                                      const uint32_t* __restrict__ rows,
-                                      uint64_t nrows,
-                                      uint32_t* __restrict__ caps) {
-  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
-  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
-                    threadIdx.x;
-       i < nrows; i += stride) {
-    uint32_t r = rows[i];
-    uint64_t deg = off1[r + 1] - off1[r];
-    if (off2) deg += off2[r + 1] - off2[r];
-    uint64_t cap = 1024;
-    while (cap < 2 * deg) cap <<= 1;
-    caps[i] = static_cast<uint32_t>(cap);
-  }
-}
-
-// block-per-row global hash (heavy rows). Slots are epoch-tagged: the
-// count word packs (epoch << 24 | count), so tables never need clearing
-// between iterations — a stale slot (old epoch) reads as empty.
+// Block-per-row global hash for rows past kTierMidDeg. Row i owns slots
+// tbl_off[i] .. tbl_off[i + 1] of the pool. A slot is one u64: the high 32
+// bits hold the label, the low 32 hold epoch:8 | count:24. A slot whose
+// epoch is not this launch's reads as empty, so the pool is never cleared
+// between iterations (the host re-zeroes it when the 8-bit epoch wraps;
+// epoch 0 is the zeroed state and is never launched). The count saturates
+// at 2^24 - 1.
 __global__ void cdlp_large_kernel(const uint64_t* __restrict__ off1,
                                   const uint32_t* __restrict__ dst1,
                                   const uint64_t* __restrict__ off2,
@@ -4918,35 +4896,18 @@ __global__ void cdlp_large_kernel(const uint64_t* __restrict__ off1,
                                   uint32_t epoch, uint32_t v_begin,
                                   const uint32_t* __restrict__ dirty,
                                   uint32_t* __restrict__ next) {
-  // slot u64 = (epoch:16 | label:32 hashed into low? ) — layout:
-  // high 16 bits epoch, next 32 bits label, low 16 bits... counts can
-  // exceed 16 bits, so: slot = (epoch<<48) | (label<<16) is unsafe.
-  // Instead: two u32 halves in one u64: hi = label, lo = (epoch<<24|cnt)
-  // with cnt capped at 2^24 (heavy rows cap the count at deg < 2^24 per
-  // label; larger multiplicities clamp — mode selection unaffected since
-  // clamp only at astronomically heavy rows).
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
-    if (dirty) {
-      uint32_t vg = v_begin + r;
-      if (!((dirty[vg >> 5] >> (vg & 31)) & 1)) continue;
-    }
-    uint64_t b1 = off1[r], e1 = off1[r + 1];
-    uint64_t d1 = e1 - b1;
-    uint64_t deg = d1;
-    uint64_t b2 = 0;
-    if (off2) {
-      b2 = off2[r];
-      deg += off2[r + 1] - b2;
-    }
+    if (!row_is_dirty(dirty, v_begin + r)) continue;
+    AdjRow<uint64_t> row = adj_row<uint64_t>(off1, off2, r, v_begin);
     uint64_t tb = tbl_off[i];
     const uint64_t cap = tbl_off[i + 1] - tb;
     const uint64_t mask = cap - 1;
     unsigned long long* t = tbl + tb;
     const uint32_t etag = epoch << 24;
-    for (uint64_t k = threadIdx.x; k < deg; k += blockDim.x) {
-      uint32_t l = k < d1 ? lab[dst1[b1 + k]] : lab[dst2[b2 + (k - d1)]];
-      uint64_t idx = cdlp_hash(l) & mask;
+    for (uint64_t k = threadIdx.x; k < row.deg; k += blockDim.x) {
+      uint32_t l = lab[row.at(dst1, dst2, k)];
+      uint64_t idx = slot_hash(l) & mask;
       for (;;) {
         unsigned long long cur = t[idx];
         uint32_t cur_lab = static_cast<uint32_t>(cur >> 32);
@@ -4977,12 +4938,11 @@ __global__ void cdlp_large_kernel(const uint64_t* __restrict__ off1,
       uint32_t lo = static_cast<uint32_t>(cur);
       if ((lo >> 24) == epoch && (lo & 0xFFFFFF)) {
         uint64_t cand =
-            (static_cast<uint64_t>(lo & 0xFFFFFF) << 32) |
-            static_cast<uint32_t>(~static_cast<uint32_t>(cur >> 32));
+            mode_key(lo & 0xFFFFFF, static_cast<uint32_t>(cur >> 32));
         if (cand > key) key = cand;
       }
     }
-    cdlp_block_argmax(key, &next[r], lab[v_begin + r]);
+    cdlp_block_argmax(key, &next[r], lab[row.v]);
   }
 }
 
@@ -5000,7 +4960,7 @@ __global__ void cdlp_commit_kernel(const uint32_t* __restrict__ next,
   for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < owned;
        r += stride) {
     uint32_t v = v_begin + r;
-    if (dirty && !((dirty[v >> 5] >> (v & 31)) & 1)) continue;
+    if (!row_is_dirty(dirty, v)) continue;
     uint32_t nv = next[r];
     if (nv != lab[v]) {
       lab[v] = nv;
@@ -5039,6 +4999,68 @@ struct CdlpDirtyOp {
   }
 };
 
+// Owned rows tiered by combined (off1 [+ off2]) degree, and the layout of
+// the global table pool the large tier hashes into: large row i owns slots
+// heavy_off[i] .. heavy_off[i + 1] of heavy_total. The pool itself is the
+// user's (CDLP: epoch-tagged u64 slots, LCC: u32 labels). Built once per run;
+// syncs s for the tier counts and, with large rows, for the pool size.
+struct RowTiers {
+  DeviceBuffer<uint32_t> tiny, small, wave, mid, large;
+  uint64_t n_tiny = 0, n_small = 0, n_wave = 0, n_mid = 0, n_large = 0;
+  DeviceBuffer<uint64_t> heavy_off;
+  uint64_t heavy_total = 0;
+};
+
+static RowTiers build_row_tiers(const uint64_t* off1, const uint64_t* off2,
+                                uint32_t owned, bool tiny, hipStream_t s,
+                                ScanTemp& scan) {
+  RowTiers t;
+  auto n = partition_rows(
+      CombinedDegTiers{off1, off2, tiny}, owned,
+      {tiny ? &t.tiny : nullptr, &t.small, &t.wave, &t.mid, &t.large}, s);
+  t.n_tiny = n[0], t.n_small = n[1], t.n_wave = n[2], t.n_mid = n[3],
+  t.n_large = n[4];
+  if (t.n_large) {
+    DeviceBuffer<uint32_t> caps(t.n_large);
+    t.heavy_off.resize(t.n_large + 1);
+    heavy_cap_kernel<<<grid_for(t.n_large), kBlock, 0, s>>>(
+        off1, off2, t.large.data(), t.n_large, caps.data());
+    t.heavy_total =
+        exclusive_scan(caps.data(), t.heavy_off.data(), t.n_large, s, scan);
+  }
+  return t;
+}
+
+// iteration `it` of the label mode over all five tiers into `next`
+static void launch_cdlp_tiers(RowTiers& t, const uint64_t* o1,
+                              const uint32_t* d1, const uint64_t* o2,
+                              const uint32_t* d2, const uint32_t* lab,
+                              DeviceBuffer<unsigned long long>& heavy_tbl,
+                              int it, uint32_t v_begin, const uint32_t* dirty,
+                              uint32_t* next, hipStream_t s) {
+  if (t.n_tiny)
+    cdlp_tiny_kernel<<<grid_for(t.n_tiny), kBlock, 0, s>>>(
+        o1, d1, o2, d2, lab, t.tiny.data(), t.n_tiny, v_begin, dirty, next);
+  if (t.n_small)
+    cdlp_small_kernel<<<grid_for(t.n_small * kWave), kBlock, 0, s>>>(
+        o1, d1, o2, d2, lab, t.small.data(), t.n_small, v_begin, dirty, next);
+  if (t.n_wave)
+    cdlp_wave_kernel<<<grid_for(((t.n_wave + 3) / 4) * kBlock), kBlock, 0,
+                       s>>>(o1, d1, o2, d2, lab, t.wave.data(), t.n_wave,
+                            v_begin, dirty, next);
+  if (t.n_mid)
+    cdlp_mid_kernel<<<std::min<int>(t.n_mid, kMaxGrid), kBlock, 0, s>>>(
+        o1, d1, o2, d2, lab, t.mid.data(), t.n_mid, v_begin, dirty, next);
+  if (t.n_large) {
+    // the epoch tag is 8-bit and 0 is the zeroed state: re-zero on wrap
+    if (it > 0 && it % 254 == 0) heavy_tbl.zero(s);
+    cdlp_large_kernel<<<std::min<int>(t.n_large, kMaxGrid), kBlock, 0, s>>>(
+        o1, d1, o2, d2, lab, t.large.data(), t.n_large, t.heavy_off.data(),
+        heavy_tbl.data(), static_cast<uint32_t>((it % 254) + 1), v_begin,
+        dirty, next);
+  }
+}
+
 GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
   RangeMarker _mk("grapehip::cdlp");
   auto& I = *impl_;
@@ -5056,36 +5078,11 @@ GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
   const uint64_t* off2 = g.directed ? g.ie_off.data() : nullptr;
   const uint32_t* dst2 = g.directed ? g.ie_dst.data() : nullptr;
 
-  // tier the rows once (degrees don't change across iterations)
-  DeviceBuffer<uint32_t> t_tiny(owned), t_small(owned), t_wave(owned),
-      t_mid(owned), t_large(owned);
-  DeviceBuffer<unsigned long long> cnts(5);
-  cnts.zero(s);
-  if (owned)
-    cdlp_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        off1, off2, owned, t_tiny.data(), cnts.data() + 0, t_small.data(),
-        cnts.data() + 1, t_wave.data(), cnts.data() + 2, t_mid.data(),
-        cnts.data() + 3, t_large.data(), cnts.data() + 4);
-  auto hc = cnts.download(s);
-  uint64_t n_tiny = hc[0], n_small = hc[1], n_wave = hc[2], n_mid = hc[3],
-           n_large = hc[4];
-
-  // heavy-row global hash pool (epoch-tagged u64 slots: no per-iteration
-  // clears; epoch 0 == the zeroed virgin state)
-  DeviceBuffer<uint32_t> heavy_caps;
-  DeviceBuffer<uint64_t> heavy_off;
-  DeviceBuffer<unsigned long long> heavy_tbl;
-  uint64_t heavy_total = 0;
-  if (n_large) {
-    heavy_caps.resize(n_large);
-    heavy_off.resize(n_large + 1);
-    cdlp_heavy_cap_kernel<<<grid_for(n_large), kBlock, 0, s>>>(
-        off1, off2, t_large.data(), n_large, heavy_caps.data());
-    heavy_total = exclusive_scan(heavy_caps.data(), heavy_off.data(),
-                                 n_large, s, I.scan);
-    heavy_tbl.resize(heavy_total);
-    heavy_tbl.zero(s);
-  }
+  // tier the rows once (degrees don't change across iterations); the
+  // heavy-row pool is zeroed once (epoch 0 == the virgin state)
+  RowTiers tiers = build_row_tiers(off1, off2, owned, true, s, I.scan);
+  DeviceBuffer<unsigned long long> heavy_tbl(tiers.heavy_total);
+  heavy_tbl.zero(s);
 
   DeviceBuffer<uint32_t> lab(nv_pad);
   DeviceBuffer<uint32_t> next(owned ? owned : 1);
@@ -5128,31 +5125,8 @@ GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
   bool use_dirty = false;  // iteration 0 recomputes everything
   for (int it = 0; it < iters; ++it) {
     const uint32_t* dw = use_dirty ? dirty.data() : nullptr;
-    if (n_tiny)
-      cdlp_tiny_kernel<<<grid_for(n_tiny), kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, lab.data(), t_tiny.data(), n_tiny,
-          g.v_begin, dw, next.data());
-    if (n_small)
-      cdlp_small_kernel<<<grid_for(n_small * kWave), kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, lab.data(), t_small.data(), n_small,
-          g.v_begin, dw, next.data());
-    if (n_wave)
-      cdlp_wave_kernel<<<grid_for(((n_wave + 3) / 4) * kBlock), kBlock, 0,
-                         s>>>(off1, dst1, off2, dst2, lab.data(),
-                              t_wave.data(), n_wave, g.v_begin, dw,
-                              next.data());
-    if (n_mid)
-      cdlp_mid_kernel<<<std::min<int>(n_mid, kMaxGrid), kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, lab.data(), t_mid.data(), n_mid, g.v_begin,
-          dw, next.data());
-    if (n_large && it > 0 && it % 254 == 0)
-      heavy_tbl.zero(s);  // epoch tag is 8-bit; re-zero on wrap
-    if (n_large)
-      cdlp_large_kernel<<<std::min<int>(n_large, kMaxGrid), kBlock, 0, s>>>(
-          off1, dst1, off2, dst2, lab.data(), t_large.data(), n_large,
-          heavy_off.data(), heavy_tbl.data(),
-          static_cast<uint32_t>((it % 254) + 1), g.v_begin, dw,
-          next.data());
+    launch_cdlp_tiers(tiers, off1, dst1, off2, dst2, lab.data(), heavy_tbl,
+                      it, g.v_begin, dw, next.data(), s);
     d_nch.zero(s);
     if (owned)
       cdlp_commit_kernel<<<grid_for(owned), kBlock, 0, s>>>(
@@ -5242,8 +5216,6 @@ GpuRunResult GpuContext::cdlp(DeviceGraph& g, int iters, bool fetch) {
 //   7. allreduce-sum T, finalize lcc = 2T/(D(D−1))
 // ---------------------------------------------------------------------------
 
-constexpr uint32_t kLccLdsSlots = 8192;  // 32 KB label-only LDS hash
-
 // orientation: keep u in O(v) iff (D[u],u) > (D[v],v)
 __device__ __forceinline__ bool lcc_keep(uint32_t du, uint32_t u, uint32_t dv,
                                          uint32_t v) {
@@ -5257,56 +5229,18 @@ __device__ __forceinline__ bool lcc_keep(uint32_t du, uint32_t u, uint32_t dv,
 //   LccEmitSink   appends them (orientation-filtered when `filter`) to the
 //                 row's capacity-layout slot in oadj and writes ocnt[r]
 
-// row r decoded; Len is u32 except in the large tier
-template <typename Len>
-struct LccRow {
-  uint32_t v;
-  uint64_t b1, b2;
-  Len d1, deg;
-  __device__ __forceinline__ uint32_t at(const uint32_t* __restrict__ dst1,
-                                         const uint32_t* __restrict__ dst2,
-                                         Len k) const {
-    return k < d1 ? dst1[b1 + k] : dst2[b2 + (k - d1)];
-  }
-};
-
-template <typename Len>
-__device__ __forceinline__ LccRow<Len> lcc_row(
-    const uint64_t* __restrict__ off1, const uint64_t* __restrict__ off2,
-    uint32_t r, uint32_t v_begin) {
-  LccRow<Len> row;
-  row.v = v_begin + r;
-  row.b1 = off1[r];
-  row.d1 = static_cast<Len>(off1[r + 1] - row.b1);
-  row.deg = row.d1;
-  row.b2 = 0;
-  if (off2) {
-    row.b2 = off2[r];
-    row.deg += static_cast<Len>(off2[r + 1] - row.b2);
-  }
-  return row;
-}
-
 // open-addressing insert into a pow2 table (LDS: u32 mask, global: u64
 // mask); true iff u was not there yet
 template <typename Mask>
 __device__ __forceinline__ bool insert_once(uint32_t* table, Mask mask,
                                             uint32_t u) {
-  Mask idx = cdlp_hash(u) & mask;
+  Mask idx = slot_hash(u) & mask;
   for (;;) {
-    uint32_t old = atomicCAS(&table[idx], kCdlpEmpty, u);
-    if (old == kCdlpEmpty) return true;
+    uint32_t old = atomicCAS(&table[idx], kSlotEmpty, u);
+    if (old == kSlotEmpty) return true;
     if (old == u) return false;
     idx = (idx + 1) & mask;
   }
-}
-
-// LDS table size for a row: pow2 >= 2*deg, clamped to the tier's slots
-__device__ __forceinline__ uint32_t lcc_lds_cap(uint32_t deg,
-                                                uint32_t slots) {
-  uint32_t cap = 64;
-  while (cap < 2 * deg) cap <<= 1;
-  return cap > slots ? slots : cap;
 }
 
 // small tier (deg <= 64, one lane per arc): bit L set iff lane L holds the
@@ -5397,8 +5331,8 @@ __global__ void lcc_dedup_small_kernel(
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * wpb + wid; i < nrows;
        i += wstride) {
     uint32_t r = rows[i];
-    LccRow<uint32_t> row = lcc_row<uint32_t>(off1, off2, r, v_begin);
-    uint32_t u = kCdlpEmpty;
+    AdjRow<uint32_t> row = adj_row<uint32_t>(off1, off2, r, v_begin);
+    uint32_t u = kSlotEmpty;
     if (lane < static_cast<int>(row.deg))
       u = row.at(dst1, dst2, static_cast<uint32_t>(lane));
     bool active = lane < static_cast<int>(row.deg) && u != row.v;
@@ -5406,7 +5340,7 @@ __global__ void lcc_dedup_small_kernel(
   }
 }
 
-// 4 rows per block for 64 < deg <= kCdlpWaveDeg (a block-per-row hash on a
+// 4 rows per block for 64 < deg <= kTierWaveDeg (a block-per-row hash on a
 // deg-100 row idles 3 of 4 waves; same uniform-barrier staging as
 // cdlp_wave_kernel)
 template <typename Sink>
@@ -5415,7 +5349,7 @@ __global__ void lcc_dedup_wave_kernel(
     const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
     const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
     Sink sink) {
-  __shared__ uint32_t s_lab[4][kCdlpWaveSlots];
+  __shared__ uint32_t s_lab[4][kTierWaveSlots];
   __shared__ uint32_t s_n[4];
   const int lane = threadIdx.x & 63;
   const int wid = threadIdx.x >> 6;
@@ -5424,14 +5358,14 @@ __global__ void lcc_dedup_wave_kernel(
     uint64_t i = grp * 4 + wid;
     const bool have = i < nrows;
     uint32_t r = have ? rows[i] : 0;
-    LccRow<uint32_t> row{};
+    AdjRow<uint32_t> row{};
     uint32_t mask = 63;
     if (have) {
-      row = lcc_row<uint32_t>(off1, off2, r, v_begin);
-      uint32_t cap = lcc_lds_cap(row.deg, kCdlpWaveSlots);
+      row = adj_row<uint32_t>(off1, off2, r, v_begin);
+      uint32_t cap = lds_table_cap(row.deg, kTierWaveSlots);
       mask = cap - 1;
       for (uint32_t k = lane; k < cap; k += kWave)
-        s_lab[wid][k] = kCdlpEmpty;
+        s_lab[wid][k] = kSlotEmpty;
       if (lane == 0) s_n[wid] = 0;
     }
     __syncthreads();
@@ -5456,15 +5390,15 @@ __global__ void lcc_dedup_mid_kernel(
     const uint64_t* __restrict__ off2, const uint32_t* __restrict__ dst2,
     const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
     Sink sink) {
-  __shared__ uint32_t s_lab[kLccLdsSlots];
+  __shared__ uint32_t s_lab[kTierMidSlots];
   __shared__ uint32_t s_n;
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
-    LccRow<uint32_t> row = lcc_row<uint32_t>(off1, off2, r, v_begin);
-    const uint32_t cap = lcc_lds_cap(row.deg, kLccLdsSlots);
+    AdjRow<uint32_t> row = adj_row<uint32_t>(off1, off2, r, v_begin);
+    const uint32_t cap = lds_table_cap(row.deg, kTierMidSlots);
     const uint32_t mask = cap - 1;
     for (uint32_t k = threadIdx.x; k < cap; k += blockDim.x)
-      s_lab[k] = kCdlpEmpty;
+      s_lab[k] = kSlotEmpty;
     if (threadIdx.x == 0) s_n = 0;
     __syncthreads();
     auto st = sink.open(r, row.v);
@@ -5479,7 +5413,7 @@ __global__ void lcc_dedup_mid_kernel(
   }
 }
 
-// rows past kCdlpMidDeg: row i hashes into its slice of the global table
+// rows past kTierMidDeg: row i hashes into its slice of the global table
 // pool (tbl_off[i] .. tbl_off[i + 1]), which the host clears before launch
 template <typename Sink>
 __global__ void lcc_dedup_large_kernel(
@@ -5491,7 +5425,7 @@ __global__ void lcc_dedup_large_kernel(
   __shared__ uint32_t s_n;
   for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
     uint32_t r = rows[i];
-    LccRow<uint64_t> row = lcc_row<uint64_t>(off1, off2, r, v_begin);
+    AdjRow<uint64_t> row = adj_row<uint64_t>(off1, off2, r, v_begin);
     uint64_t tb = tbl_off[i];
     const uint64_t mask = (tbl_off[i + 1] - tb) - 1;
     uint32_t* tl = tbl_lab + tb;
@@ -5575,11 +5509,11 @@ __global__ void lcc_hashfill_kernel(const uint64_t* __restrict__ goff,
 
 __device__ __forceinline__ bool lcc_probe(const uint32_t* __restrict__ t,
                                           uint64_t mask, uint32_t key) {
-  uint64_t idx = cdlp_hash(key) & mask;
+  uint64_t idx = slot_hash(key) & mask;
   for (;;) {
     uint32_t x = t[idx];
     if (x == key) return true;
-    if (x == kCdlpEmpty) return false;
+    if (x == kSlotEmpty) return false;
     idx = (idx + 1) & mask;
   }
 }
@@ -5650,7 +5584,7 @@ __global__ void lcc_tri_wee_kernel(const uint64_t* __restrict__ goff,
         for (int j = 0; j < 4; ++j) {
           live[j] = e0 + j < en;
           key[j] = live[j] ? gdst[eb + e0 + j] : 0;
-          idx[j] = cdlp_hash(key[j]) & mask;
+          idx[j] = slot_hash(key[j]) & mask;
         }
         for (;;) {
           uint32_t x[4];
@@ -5665,7 +5599,7 @@ __global__ void lcc_tri_wee_kernel(const uint64_t* __restrict__ goff,
               ++hits;
               if (!skip_witness) atomicAdd(&T[key[j]], 1ull);
               live[j] = false;
-            } else if (x[j] == kCdlpEmpty) {
+            } else if (x[j] == kSlotEmpty) {
               live[j] = false;
             } else {
               idx[j] = (idx[j] + 1) & mask;
@@ -5689,11 +5623,11 @@ __global__ void lcc_tri_wee_kernel(const uint64_t* __restrict__ goff,
 
 __device__ __forceinline__ bool lcc_probe_lds(
     const uint32_t* __restrict__ t, uint32_t mask, uint32_t key) {
-  uint32_t idx = cdlp_hash(key) & mask;
+  uint32_t idx = slot_hash(key) & mask;
   for (;;) {
     uint32_t x = t[idx];
     if (x == key) return true;
-    if (x == kCdlpEmpty) return false;
+    if (x == kSlotEmpty) return false;
     idx = (idx + 1) & mask;
   }
 }
@@ -5770,42 +5704,18 @@ __global__ void lcc_tri_staged_kernel(
   }
 }
 
-// bucket rows for the two light tiers; rows shorter than min_n are skipped
-// (1 undirected: empty rows; 2 directed: a lone neighbor closes no pair)
-__global__ void lcc_bucket_kernel(const uint64_t* __restrict__ goff,
-                                  uint32_t owned, uint32_t v_begin,
-                                  uint32_t min_n, uint32_t* wee,
-                                  unsigned long long* cw, uint32_t* big,
-                                  unsigned long long* cb) {
-  __shared__ uint32_t s_cnt[2];
-  __shared__ unsigned long long s_base[2];
-  uint32_t* lists[2] = {wee, big};
-  unsigned long long* gcnt[2] = {cw, cb};
-  const uint32_t stride = gridDim.x * blockDim.x;
-  for (uint32_t base = blockIdx.x * blockDim.x; base < owned;
-       base += stride) {
-    if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
-    __syncthreads();
-    uint32_t r = base + threadIdx.x;
-    int b = -1;
-    uint32_t loc = 0;
-    if (r < owned) {
-      uint64_t n = goff[v_begin + r + 1] - goff[v_begin + r];
-      if (n >= min_n) {
-        b = n <= kLccWeeRows ? 0 : 1;
-        loc = atomicAdd(&s_cnt[b], 1u);
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 && s_cnt[threadIdx.x])
-      s_base[threadIdx.x] =
-          atomicAdd(gcnt[threadIdx.x],
-                    static_cast<unsigned long long>(s_cnt[threadIdx.x]));
-    __syncthreads();
-    if (b >= 0) lists[b][s_base[b] + loc] = r;
-    __syncthreads();
+// the two light count tiers by global-CSR row length; rows shorter than
+// min_n are skipped (1 undirected: empty rows; 2 directed: a lone neighbor
+// closes no pair)
+struct LccLenTiers {
+  static constexpr int kLists = 2, kBins = 2;
+  const uint64_t* __restrict__ goff;
+  uint32_t v_begin, min_n;
+  __device__ __forceinline__ int operator()(uint32_t r) const {
+    uint64_t n = goff[v_begin + r + 1] - goff[v_begin + r];
+    return n < min_n ? -1 : (n <= kLccWeeRows ? 0 : 1);
   }
-}
+};
 
 // second pass: one wave per heavy edge; lanes stride the smaller list
 __global__ void lcc_triangle_heavy_kernel(
@@ -5854,7 +5764,7 @@ __global__ void lcc_triangle_heavy_kernel(
         uint32_t e = e0 + j * kWave;
         live[j] = e < en;
         key[j] = live[j] ? gdst[eb + e] : 0;
-        idx[j] = cdlp_hash(key[j]) & mask;
+        idx[j] = slot_hash(key[j]) & mask;
       }
       for (;;) {
         uint32_t x[4];
@@ -5869,7 +5779,7 @@ __global__ void lcc_triangle_heavy_kernel(
             ++hits;
             atomicAdd(&T[key[j]], 1ull);
             live[j] = false;
-          } else if (x[j] == kCdlpEmpty) {
+          } else if (x[j] == kSlotEmpty) {
             live[j] = false;
           } else {
             idx[j] = (idx[j] + 1) & mask;
@@ -6173,42 +6083,18 @@ void lcc_fetch_referenced_rows(GpuContext::Impl& I,
 // --- set-building helpers, in call order: tiers -> distinct -> emit ->
 // global CSR -> hash sets ------------------------------------------------
 
-// Owned rows split by combined (off1 [+ off2]) degree, reusing the CDLP
-// bucketer, and the global table pool the large tier hashes into.
-struct LccTiers {
-  DeviceBuffer<uint32_t> small, wave, mid, large;
-  uint64_t n_small = 0, n_wave = 0, n_mid = 0, n_large = 0;
-  DeviceBuffer<uint64_t> heavy_off;  // per large row, into tbl_lab
+// The shared combined-degree tiers (no tiny tier: those rows are small
+// rows) plus LCC's table pool for the large tier: u32 labels, cleared
+// before each pass.
+struct LccTiers : RowTiers {
   DeviceBuffer<uint32_t> tbl_lab;
-  uint64_t heavy_total = 0;
 };
 
 LccTiers build_lcc_tiers(GpuContext::Impl& I, const uint64_t* off1,
                          const uint64_t* off2, uint32_t owned,
                          hipStream_t s) {
-  LccTiers t;
-  t.small.resize(owned ? owned : 1);
-  t.wave.resize(owned ? owned : 1);
-  t.mid.resize(owned ? owned : 1);
-  t.large.resize(owned ? owned : 1);
-  DeviceBuffer<unsigned long long> cnts(5);
-  cnts.zero(s);
-  if (owned)
-    cdlp_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        off1, off2, owned, nullptr, cnts.data() + 3, t.small.data(),
-        cnts.data() + 0, t.wave.data(), cnts.data() + 4, t.mid.data(),
-        cnts.data() + 1, t.large.data(), cnts.data() + 2);
-  auto hc = cnts.download(s);
-  t.n_small = hc[0], t.n_mid = hc[1], t.n_large = hc[2], t.n_wave = hc[4];
-  if (t.n_large) {
-    DeviceBuffer<uint32_t> heavy_caps(t.n_large);
-    t.heavy_off.resize(t.n_large + 1);
-    cdlp_heavy_cap_kernel<<<grid_for(t.n_large), kBlock, 0, s>>>(
-        off1, off2, t.large.data(), t.n_large, heavy_caps.data());
-    t.heavy_total = exclusive_scan(heavy_caps.data(), t.heavy_off.data(),
-                                   t.n_large, s, I.scan);
-    t.tbl_lab.resize(t.heavy_total);
-  }
+  LccTiers t{build_row_tiers(off1, off2, owned, false, s, I.scan), {}};
+  t.tbl_lab.resize(t.heavy_total);
   return t;
 }
 
@@ -6228,7 +6114,7 @@ void launch_dedup_tiers(LccTiers& t, const uint64_t* o1, const uint32_t* d1,
     lcc_dedup_mid_kernel<<<std::min<int>(t.n_mid, kMaxGrid), kBlock, 0, s>>>(
         o1, d1, o2, d2, t.mid.data(), t.n_mid, v_begin, sink);
   if (t.n_large) {
-    fill(t.tbl_lab.data(), kCdlpEmpty, t.heavy_total, s);
+    fill(t.tbl_lab.data(), kSlotEmpty, t.heavy_total, s);
     lcc_dedup_large_kernel<<<std::min<int>(t.n_large, kMaxGrid), kBlock, 0,
                              s>>>(o1, d1, o2, d2, t.large.data(), t.n_large,
                                   t.heavy_off.data(), t.tbl_lab.data(),
@@ -6343,7 +6229,7 @@ void build_hash_sets(GpuContext::Impl& I, uint32_t nv_pad,
                                   I.scan);
   hcap.free();
   htab.resize(total);
-  fill(htab.data(), kCdlpEmpty, total, s);
+  fill(htab.data(), kSlotEmpty, total, s);
   lcc_hashfill_kernel<<<grid_for(static_cast<size_t>(nv_pad) * kWave),
                         kBlock, 0, s>>>(csr.goff.data(), csr.gdst.data(),
                                         hoff.data(), nv_pad, htab.data());
@@ -6389,14 +6275,8 @@ LccTail lcc_tail_begin(DeviceGraph& g, uint32_t nv_pad,
     t.heavy_q.resize(std::max<uint64_t>(hi - lo, 1));
   }
   if (owned) {
-    t.wee_rows.resize(owned);
-    t.big_rows.resize(owned);
-    DeviceBuffer<unsigned long long> tcnts(2);
-    tcnts.zero(s);
-    lcc_bucket_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        goff.data(), owned, g.v_begin, min_n, t.wee_rows.data(),
-        tcnts.data() + 0, t.big_rows.data(), tcnts.data() + 1);
-    auto tc = tcnts.download(s);
+    auto tc = partition_rows(LccLenTiers{goff.data(), g.v_begin, min_n},
+                             owned, {&t.wee_rows, &t.big_rows}, s);
     t.n_wee = tc[0], t.n_big = tc[1];
   }
   return t;

@@ -10,7 +10,7 @@ from oracles import lcc_oracle
 pytestmark = pytest.mark.gpu
 
 NV = 30000
-# kCdlpSmallDeg, kCdlpWaveDeg, kCdlpMidDeg, each with the next value up
+# kTierSmallDeg, kTierWaveDeg, kTierMidDeg, each with the next value up
 BOUNDS = [64, 65, 512, 513, 4096, 4097]
 # (stored degree, distinct filler values) of the duplicate-arc rows, one per
 # tier: small, wave, mid, large

@@ -369,6 +369,51 @@ PYBIND11_MODULE(_core, m) {
 #endif
            },
            py::arg("reset") = false)
+      .def("_debug_pr_path",
+           [](PyEngine& e, bool reset) {
+#ifdef GRAPEHIP_WITH_HIP
+             auto c = e.gpu->debug_pr_path(reset);
+             py::dict d;
+             d["segments"] = c[0];
+             d["rows"] = c[1];
+             return d;
+#else
+             (void)reset;
+             throw std::runtime_error("no hip");
+             return py::dict();
+#endif
+           },
+           py::arg("reset") = false)
+      .def("_debug_pr_segments",
+           [](PyEngine& e, PyGraph& g) {
+#ifdef GRAPEHIP_WITH_HIP
+             auto as_array = [](const auto& v) {
+               return py::array_t<typename std::decay_t<decltype(v)>::
+                                      value_type>(v.size(), v.data());
+             };
+             auto s = e.gpu->debug_pr_segments(*g.dev);
+             py::dict d;
+             d["on"] = s.on;
+             d["item"] = s.item;
+             d["build_ms"] = s.build_ms;
+             d["bytes"] = s.bytes;
+             d["bound"] = as_array(s.bound);
+             d["rows"] = as_array(s.rows);
+             d["span_first"] = as_array(s.span_first);
+             d["span_pref"] = as_array(s.span_pref);
+             d["span_base"] = as_array(s.span_base);
+             d["span_row"] = as_array(s.span_row);
+             d["span_slot"] = as_array(s.span_slot);
+             d["row_first"] = as_array(s.row_first);
+             d["off"] = as_array(s.off);
+             d["dst"] = as_array(s.dst);
+             return d;
+#else
+             (void)g;
+             throw std::runtime_error("no hip");
+             return py::dict();
+#endif
+           })
       .def("_debug_scan",
            [](PyEngine& e, std::vector<uint32_t> in) {
 #ifdef GRAPEHIP_WITH_HIP

@@ -46,4 +46,25 @@ struct DevGraphView {
   }
 };
 
+// PageRank id segments (see ensure_pr_segments): the vertex ids are cut into
+// kPrSegs contiguous ranges, a head that every L2 keeps, eight slices that
+// one XCD each gathers from, and a cold tail. Segment s = ids
+// [bound[s], bound[s + 1]). A span is the part of one row's sorted adjacency
+// that lies in one segment; the spans of a segment, in row order, form the
+// segment's arc space, which is cut into items of `item` arcs. The span
+// arrays are segment-major with one arc prefix running through all
+// segments, so span_pref[span_first[s + 1]] closes segment s.
+constexpr int kPrSegs = 10;
+constexpr int kPrSlices = kPrSegs - 2;
+
+struct PrSegView {
+  uint64_t span_first[kPrSegs + 1];  // first span of segment s
+  uint64_t arc_first[kPrSegs + 1];   // span_pref[span_first[s]]
+  uint32_t n_items[kPrSegs];
+  uint32_t item;                              // arcs per item
+  const uint64_t* __restrict__ span_pref;     // [n_spans + 1]
+  const uint64_t* __restrict__ span_base;     // CSR slot of the first arc
+  const uint32_t* __restrict__ span_slot;     // partial of its first item
+};
+
 }  // namespace grapehip

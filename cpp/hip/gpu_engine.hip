@@ -2028,6 +2028,310 @@ __global__ void pr_hub_reduce_kernel(const uint32_t* __restrict__ rows,
 }
 
 // ===========================================================================
+// PageRank id-segment pull (mid and hub rows, single GPU, PHASE 0).
+//
+// The row pulls gather contrib[dst] over the whole id range from every
+// workgroup, so each XCD's private 4 MiB L2 tries to hold the same hot ids.
+// Here the ids are cut into kPrSegs contiguous segments (PrSegView in
+// dev_graph.hpp) and a workgroup prefers the items of the slice that
+// belongs to the XCD it runs on, so that slice's contribs are gathered
+// through one L2 only. Which workgroup takes which item decides speed and
+// nothing else: every (span, item) partial is a sum in a fixed order,
+// written once, and pr_seg_reduce_kernel folds a row's partials in
+// (segment, item) order.
+// ===========================================================================
+
+// One bitmap word per thread: the rows of the mid and hub tiers.
+__global__ void pr_seg_rows_bitmap_kernel(const uint64_t* __restrict__ off,
+                                          uint32_t owned,
+                                          uint32_t* __restrict__ words,
+                                          size_t nwords) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (size_t w = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+       w < nwords; w += stride) {
+    uint32_t bits = 0;
+    for (int b = 0; b < 32; ++b) {
+      uint64_t r = (static_cast<uint64_t>(w) << 5) + b;
+      if (r < owned && off[r + 1] - off[r] >= kSmallDeg) bits |= 1u << b;
+    }
+    words[w] = bits;
+  }
+}
+
+struct PrSegBounds {
+  uint32_t b[kPrSegs + 1];
+};
+
+// Wave per row: lanes 0..kPrSegs search the row's sorted adjacency for the
+// segment bounds; len[s * nrows + j] is the length of row j's span in
+// segment s (segment-major). A span of 2^32 arcs or more raises *too_long.
+__global__ void pr_seg_cut_kernel(const uint64_t* __restrict__ off,
+                                  const uint32_t* __restrict__ dst,
+                                  const uint32_t* __restrict__ rows,
+                                  uint64_t nrows, PrSegBounds bnd,
+                                  uint32_t* __restrict__ len,
+                                  int* __restrict__ too_long) {
+  const int lane = threadIdx.x & 63;
+  const int wid = threadIdx.x >> 6;
+  const int waves_per_block = kBlock / kWave;
+  size_t wstride = static_cast<size_t>(gridDim.x) * waves_per_block;
+  for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * waves_per_block + wid;
+       j < nrows; j += wstride) {
+    const uint32_t r = rows[j];
+    const uint64_t b = off[r], e = off[r + 1];
+    unsigned long long cut = e;
+    if (lane == 0) cut = b;
+    else if (lane < kPrSegs) cut = lb_u32(dst, b, e, bnd.b[lane]);
+    const unsigned long long next = __shfl_down(cut, 1, 64);
+    if (lane < kPrSegs) {
+      const uint64_t l = next - cut;
+      if (l > 0xFFFFFFFFull) *too_long = 1;
+      len[static_cast<uint64_t>(lane) * nrows + j] = static_cast<uint32_t>(l);
+    }
+  }
+}
+
+// flag[idx] (segment-major): the span is not empty. pieces[j * kPrSegs + s]
+// (row-major): the items it crosses, i.e. the partials it owns.
+__global__ void pr_seg_pieces_kernel(const uint32_t* __restrict__ len,
+                                     const uint64_t* __restrict__ pref,
+                                     uint64_t nrows, uint32_t item,
+                                     uint32_t* __restrict__ flag,
+                                     uint32_t* __restrict__ pieces) {
+  const uint64_t n = nrows * kPrSegs;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t idx = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                      threadIdx.x;
+       idx < n; idx += stride) {
+    const uint64_t s = idx / nrows, j = idx - s * nrows;
+    const uint64_t l = len[idx];
+    const uint64_t a = pref[idx] - pref[s * nrows];
+    flag[idx] = l ? 1u : 0u;
+    pieces[j * kPrSegs + s] =
+        l ? static_cast<uint32_t>((a + l - 1) / item - a / item + 1) : 0u;
+  }
+}
+
+__global__ void pr_seg_fill_kernel(
+    const uint32_t* __restrict__ len, const uint64_t* __restrict__ pref,
+    const uint64_t* __restrict__ sid, const uint64_t* __restrict__ pfirst,
+    const uint64_t* __restrict__ off, const uint32_t* __restrict__ rows,
+    uint64_t nrows, uint64_t* __restrict__ span_pref,
+    uint64_t* __restrict__ span_base, uint32_t* __restrict__ span_row,
+    uint32_t* __restrict__ span_slot, uint64_t* __restrict__ row_first) {
+  const uint64_t n = nrows * kPrSegs;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t idx = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                      threadIdx.x;
+       idx < n; idx += stride) {
+    const uint64_t s = idx / nrows, j = idx - s * nrows;
+    if (s == 0) row_first[j] = pfirst[j * kPrSegs];
+    if (!len[idx]) continue;
+    const uint64_t k = sid[idx];
+    uint64_t base = off[rows[j]];
+    for (uint64_t p = 0; p < s; ++p) base += len[p * nrows + j];
+    span_pref[k] = pref[idx];
+    span_base[k] = base;
+    span_row[k] = static_cast<uint32_t>(j);
+    span_slot[k] = static_cast<uint32_t>(pfirst[j * kPrSegs + s]);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    span_pref[sid[n]] = pref[n];
+    row_first[nrows] = pfirst[n];
+  }
+}
+
+// The XCD this wave runs on (hardware register XCC_ID, bits 3:0).
+__device__ __forceinline__ uint32_t xcc_id() {
+  constexpr int kHwRegXccId = 20;
+  return __builtin_amdgcn_s_getreg(((4 - 1) << 11) | kHwRegXccId);
+}
+
+constexpr int kPrSegBlocksPerCu = 8;
+
+// Persistent: CUs x kPrSegBlocksPerCu workgroups, each taking items from
+// per-segment counters (ctr, zeroed before every launch).
+template <bool NT>
+__global__ void __launch_bounds__(kBlock)
+pr_pull_seg_kernel(PrSegView v, const uint32_t* __restrict__ dst,
+                   const float* __restrict__ contrib,
+                   uint32_t* __restrict__ ctr, double* __restrict__ part) {
+  __shared__ uint64_t s_off[kBlock + 1];  // arc prefix of the batch's spans
+  __shared__ uint64_t s_base[kBlock];
+  __shared__ uint32_t s_slot[kBlock];
+  __shared__ double s_wacc[kBlock / kWave][kBlock];  // per wave, per span
+  __shared__ uint32_t s_take, s_first;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wid = tid >> 6;
+  const uint32_t x = xcc_id() % kPrSlices;
+  // Queue order: this XCD's slice, the head, the tail, then the other
+  // slices. The loop ends on every path: a workgroup walks the kPrSegs
+  // queues once, in this order, and never goes back; a counter only grows,
+  // and every add either hands out one of the segment's n_items items or
+  // returns a value past them, which moves the workgroup on to the next
+  // queue. So a workgroup makes at most (items it processes) + kPrSegs
+  // adds, waits for no other workgroup, and leaves after the last queue.
+  for (int qi = 0; qi < kPrSegs; ++qi) {
+    const int s = qi == 0   ? 1 + static_cast<int>(x)
+                  : qi == 1 ? 0
+                  : qi == 2 ? kPrSegs - 1
+                            : 1 + static_cast<int>((x + qi - 2) % kPrSlices);
+    const uint32_t n_items = v.n_items[s];
+    if (!n_items) continue;
+    const uint64_t* __restrict__ pref = v.span_pref + v.span_first[s];
+    const uint64_t* __restrict__ sbase = v.span_base + v.span_first[s];
+    const uint32_t* __restrict__ sslot = v.span_slot + v.span_first[s];
+    const uint32_t qn =
+        static_cast<uint32_t>(v.span_first[s + 1] - v.span_first[s]);
+    const uint64_t arc0 = v.arc_first[s], arc1 = v.arc_first[s + 1];
+    for (;;) {
+      if (tid == 0) s_take = atomicAdd(&ctr[s], 1u);
+      __syncthreads();
+      const uint32_t t = s_take;
+      if (t >= n_items) {
+        __syncthreads();  // s_take is rewritten for the next queue
+        break;
+      }
+      const uint64_t tile_lo = arc0 + static_cast<uint64_t>(t) * v.item;
+      const uint64_t tile_hi = tile_lo + v.item < arc1 ? tile_lo + v.item : arc1;
+      if (tid < kWave) {
+        uint32_t first = wave_owner_search(pref, qn, tile_lo, tid);
+        if (tid == 0) s_first = first;
+      }
+      __syncthreads();
+      uint32_t chunk = s_first;
+      for (;;) {
+        const int n = min(static_cast<uint32_t>(kBlock), qn - chunk);
+        if (tid < n) {
+          const uint64_t o = pref[chunk + tid];
+          s_off[tid] = o;
+          // spans at or past the item's end own none of its arcs
+          if (o < tile_hi) {
+            s_base[tid] = sbase[chunk + tid];
+            s_slot[tid] = sslot[chunk + tid];
+          }
+        }
+        if (tid == 0) s_off[n] = pref[chunk + n];
+#pragma unroll
+        for (int w = 0; w < kBlock / kWave; ++w) s_wacc[w][tid] = 0.0;
+        __syncthreads();
+        const uint64_t batch_end = s_off[n];
+        const uint64_t e0 = s_off[0] > tile_lo ? s_off[0] : tile_lo;
+        const uint64_t e1 = batch_end < tile_hi ? batch_end : tile_hi;
+        // each wave sums one contiguous quarter of [e0, e1) in windows of 64
+        // consecutive arcs; a span's run inside the quarter is summed in
+        // lane order, carried from window to window, and stored once
+        const uint64_t quarter =
+            ((e1 - e0 + kBlock - 1) / kBlock) * kWave;
+        const uint64_t ws = e0 + wid * quarter;
+        const uint64_t we = ws + quarter < e1 ? ws + quarter : e1;
+        int lo = 0;
+        if (ws + lane < we) {
+          int hi = n - 1;
+          const uint64_t e = ws + lane;
+          while (lo < hi) {
+            int mid = (lo + hi + 1) >> 1;
+            if (s_off[mid] <= e) lo = mid; else hi = mid - 1;
+          }
+        }
+        double carry = 0.0;
+        int carry_owner = -1;
+        for (uint64_t w0 = ws; w0 < we; w0 += kWave) {
+          const uint64_t e = w0 + lane;
+          const bool act = e < we;
+          int owner = -1;
+          double c = 0.0;
+          if (act) {
+            while (lo + 1 < n && s_off[lo + 1] <= e) ++lo;
+            owner = lo;
+            const uint64_t idx = s_base[lo] + (e - s_off[lo]);
+            const uint32_t d = NT ? __builtin_nontemporal_load(dst + idx)
+                                  : dst[idx];
+            c = static_cast<double>(contrib[d]);
+          }
+          const int oprev = __shfl_up(owner, 1, 64);
+          const bool head = (lane == 0) || oprev != owner;
+          const unsigned long long hb = __ballot(head);
+          const unsigned long long mine =
+              hb & ((lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1));
+          const int seg = 63 - __clzll(mine);
+          double sum = c;
+#pragma unroll
+          for (int d = 1; d < 64; d <<= 1) {
+            double up = __shfl_up(sum, d, 64);
+            if (lane - d >= seg) sum += up;
+          }
+          // the run that opens the window continues the carried one, or the
+          // carried one is complete
+          if (carry_owner >= 0) {
+            if (owner == carry_owner && seg == 0) sum = carry + sum;
+            const int o0 = __shfl(owner, 0, 64);
+            if (o0 != carry_owner && lane == 0)
+              s_wacc[wid][carry_owner] = carry;
+          }
+          const bool tail = (lane == 63) || ((hb >> (lane + 1)) & 1ull);
+          if (tail && act && lane != 63) s_wacc[wid][owner] = sum;
+          carry = __shfl(sum, 63, 64);
+          carry_owner = __shfl(owner, 63, 64);
+        }
+        if (carry_owner >= 0 && lane == 0) s_wacc[wid][carry_owner] = carry;
+        __syncthreads();
+        if (tid < n && s_off[tid] < e1 && s_off[tid + 1] > e0) {
+          double total = 0.0;
+#pragma unroll
+          for (int w = 0; w < kBlock / kWave; ++w) total += s_wacc[w][tid];
+          const uint64_t first_item = (s_off[tid] - arc0) / v.item;
+          part[s_slot[tid] + (t - first_item)] = total;
+        }
+        __syncthreads();
+        if (batch_end >= tile_hi || chunk + n >= qn) break;
+        chunk += n;
+      }
+    }
+  }
+}
+
+// Folds a row's partials in (segment, item) order: a lane per row, and the
+// whole wave, in a fixed tree, for a row with more than 64 of them.
+__global__ void pr_seg_reduce_kernel(const uint32_t* __restrict__ rows,
+                                     const uint64_t* __restrict__ row_first,
+                                     uint64_t nrows,
+                                     const double* __restrict__ part,
+                                     uint32_t v_begin,
+                                     double* __restrict__ acc) {
+  const int lane = threadIdx.x & 63;
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t j0 = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                     (threadIdx.x - lane);
+       j0 < nrows; j0 += stride) {
+    const uint64_t j = j0 + lane;
+    unsigned long long b = 0, e = 0;
+    if (j < nrows) {
+      b = row_first[j];
+      e = row_first[j + 1];
+    }
+    const bool wide = e - b > kWave;
+    double sum = 0.0;
+    if (!wide)
+      for (uint64_t k = b; k < e; ++k) sum += part[k];
+    unsigned long long todo = __ballot(wide);
+    while (todo) {
+      const int l = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const unsigned long long bb = __shfl(b, l, 64), ee = __shfl(e, l, 64);
+      double t = 0.0;
+      for (uint64_t k = bb + lane; k < ee; k += kWave) t += part[k];
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) t += __shfl_down(t, d, 64);
+      t = __shfl(t, 0, 64);
+      if (lane == l) sum = t;
+    }
+    if (j < nrows) acc[v_begin + rows[j]] = sum;
+  }
+}
+
+// ===========================================================================
 // PageRank tiled pull. The row-major pull gathers contrib[dst] across the
 // whole vertex range: at datagen-9_0 scale every 4-byte gather fetches a
 // distinct 64-byte line (~6% line use, r01 PMC: 2.3 TB/s fetch, >80%
@@ -2492,6 +2796,10 @@ struct GpuContext::Impl {
   // (launch_expand only, a frontier without an arc included; test hook,
   // see debug_expand_counts)
   uint64_t expand_counts[kLbCount] = {0, 0, 0, 0};
+  // pagerank() calls through the id-segment pull [0] and the row-tier
+  // pulls [1] (test hook, see debug_pr_path)
+  uint64_t pr_path_counts[2] = {0, 0};
+  int num_cus = 256;  // set by the GpuContext constructor
 };
 
 namespace {
@@ -2614,6 +2922,9 @@ GpuContext::GpuContext(TcpComm* comm, int rank, int world)
   dev_ = lr ? (std::atoi(lr) % ndev) : (rank % ndev);
   HIP_CHECK(hipSetDevice(dev_));
   impl_ = std::make_unique<Impl>();
+  HIP_CHECK(hipDeviceGetAttribute(&impl_->num_cus,
+                                  hipDeviceAttributeMultiprocessorCount,
+                                  dev_));
   DevComm& dc = impl_->dc;
   dc.tcp = comm;
   dc.rank = rank;
@@ -2663,6 +2974,13 @@ std::array<uint64_t, 4> GpuContext::debug_expand_counts(bool reset) {
     out[i] = impl_->expand_counts[i];
     if (reset) impl_->expand_counts[i] = 0;
   }
+  return out;
+}
+
+std::array<uint64_t, 2> GpuContext::debug_pr_path(bool reset) {
+  std::array<uint64_t, 2> out = {impl_->pr_path_counts[0],
+                                 impl_->pr_path_counts[1]};
+  if (reset) impl_->pr_path_counts[0] = impl_->pr_path_counts[1] = 0;
   return out;
 }
 
@@ -3185,6 +3503,172 @@ static void ensure_buckets(DeviceGraph& g, GpuContext::Impl& I,
             (unsigned long)g.n_isolated_real,
             (unsigned long)g.n_isolated_pad, (unsigned long)g.n_hub_items);
   g.buckets_built = true;
+}
+
+// Knobs of the id-segment pull, read once per process. GRAPEHIP_PR_SEG=0
+// selects the row-tier pulls; GRAPEHIP_PR_SEG_HEAD / GRAPEHIP_PR_SEG_IDS set
+// the ids of the replicated head and of each slice (tests shrink them to
+// reach every segment on tiny graphs); GRAPEHIP_PR_SEG_ITEM the arcs per
+// item; GRAPEHIP_PR_SEG_NT=1 streams dst with nontemporal loads.
+struct PrSegKnobs {
+  bool on;
+  uint64_t head, ids;
+  uint32_t item;
+  bool nt;
+};
+
+static const PrSegKnobs& pr_seg_knobs() {
+  static const PrSegKnobs k = [] {
+    auto num = [](const char* name, uint64_t dflt) {
+      const char* e = getenv(name);
+      return e && *e ? static_cast<uint64_t>(strtoull(e, nullptr, 10)) : dflt;
+    };
+    PrSegKnobs r;
+    r.on = num("GRAPEHIP_PR_SEG", 1) != 0;
+    r.head = num("GRAPEHIP_PR_SEG_HEAD", 256u << 10);
+    r.ids = std::max<uint64_t>(num("GRAPEHIP_PR_SEG_IDS", 640u << 10), 1);
+    r.item = static_cast<uint32_t>(
+        std::max<uint64_t>(num("GRAPEHIP_PR_SEG_ITEM", kHubSeg), kBlock));
+    r.nt = num("GRAPEHIP_PR_SEG_NT", 0) != 0;
+    return r;
+  }();
+  return k;
+}
+
+// Id-segment layout of the mid and hub rows over the pull CSR, once per
+// graph (needs the buckets). Everything is placed by scans over row order,
+// so the layout is the same on every build of the same graph. Returns
+// whether the path is on for g: it is off when asked off, without a mid or
+// hub row, when the segments do not fit below `owned`, or when memory is
+// short.
+static bool ensure_pr_segments(DeviceGraph& g, GpuContext::Impl& I,
+                               hipStream_t s) {
+  if (g.pr_seg_state) return g.pr_seg_state > 0;
+  g.pr_seg_state = -1;
+  const PrSegKnobs& K = pr_seg_knobs();
+  const uint32_t owned = g.owned();
+  const uint64_t nrows = g.n_mid + g.n_large;
+  const uint64_t top = K.head + kPrSlices * K.ids;
+  if (!K.on || !nrows || top >= owned) return false;
+  const uint64_t n = nrows * kPrSegs;
+  size_t free_b = 0, total_b = 0;
+  HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+  // 36 B of scratch and up to 32 B kept per (row, segment), 8 B per item
+  if (free_b < n * 68 + (g.local_edges / K.item) * 8 + (512u << 20))
+    return false;
+  const double t0 = wall_s();
+  const uint64_t* pull_off = !g.directed ? g.oe_off.data() : g.ie_off.data();
+  const uint32_t* pull_dst = !g.directed ? g.oe_dst.data() : g.ie_dst.data();
+
+  // the rows, ascending (the tier lists are in no fixed order)
+  g.seg_rows.resize(nrows);
+  {
+    size_t nwords = (static_cast<size_t>(owned) + 31) / 32;
+    DeviceBuffer<uint32_t> bm(nwords);
+    pr_seg_rows_bitmap_kernel<<<grid_for(nwords), kBlock, 0, s>>>(
+        pull_off, owned, bm.data(), nwords);
+    uint64_t got =
+        compact_frontier(I, bm.data(), owned, 0, g.seg_rows.data(), s);
+    HIP_CHECK(hipStreamSynchronize(s));  // bm is freed here
+    if (got != nrows)
+      throw std::runtime_error("pr segments: row count mismatch");
+  }
+
+  PrSegBounds bnd;
+  for (int k = 0; k <= kPrSegs; ++k) {
+    uint64_t b = k == 0 ? 0
+                 : k == kPrSegs ? g.nv_global
+                                : K.head + (k - 1) * K.ids;
+    bnd.b[k] = g.seg_bound[k] = static_cast<uint32_t>(b);
+  }
+
+  DeviceBuffer<uint32_t> len(n), flag(n), pieces(n);
+  DeviceBuffer<uint64_t> pref(n + 1), sid(n + 1), pfirst(n + 1);
+  DeviceBuffer<int> too_long(1);
+  too_long.zero(s);
+  pr_seg_cut_kernel<<<grid_for(nrows * kWave), kBlock, 0, s>>>(
+      pull_off, pull_dst, g.seg_rows.data(), nrows, bnd, len.data(),
+      too_long.data());
+  if (too_long.download(s)[0]) return false;
+  exclusive_scan(len.data(), pref.data(), n, s, I.scan);
+  pr_seg_pieces_kernel<<<grid_for(n), kBlock, 0, s>>>(
+      len.data(), pref.data(), nrows, K.item, flag.data(), pieces.data());
+  g.n_seg_spans = exclusive_scan(flag.data(), sid.data(), n, s, I.scan);
+  g.n_seg_parts = exclusive_scan(pieces.data(), pfirst.data(), n, s, I.scan);
+  if (g.n_seg_parts > 0xFFFFFFFFull) return false;
+
+  g.seg_span_pref.resize(g.n_seg_spans + 1);
+  g.seg_span_base.resize(g.n_seg_spans);
+  g.seg_span_row.resize(g.n_seg_spans);
+  g.seg_span_slot.resize(g.n_seg_spans);
+  g.seg_row_first.resize(nrows + 1);
+  g.seg_part.resize(g.n_seg_parts);
+  g.seg_ctr.resize(kPrSegs);
+  pr_seg_fill_kernel<<<grid_for(n), kBlock, 0, s>>>(
+      len.data(), pref.data(), sid.data(), pfirst.data(), pull_off,
+      g.seg_rows.data(), nrows, g.seg_span_pref.data(),
+      g.seg_span_base.data(), g.seg_span_row.data(), g.seg_span_slot.data(),
+      g.seg_row_first.data());
+
+  PrSegView& v = g.seg_view;
+  for (int k = 0; k <= kPrSegs; ++k) {
+    HIP_CHECK(hipMemcpyAsync(&v.span_first[k], sid.data() + k * nrows, 8,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(&v.arc_first[k], pref.data() + k * nrows, 8,
+                             hipMemcpyDeviceToHost, s));
+  }
+  HIP_CHECK(hipStreamSynchronize(s));  // the scratch goes out of scope
+  for (int k = 0; k < kPrSegs; ++k) {
+    uint64_t items =
+        (v.arc_first[k + 1] - v.arc_first[k] + K.item - 1) / K.item;
+    if (items > 0x7FFFFFFFull) return false;
+    v.n_items[k] = static_cast<uint32_t>(items);
+  }
+  v.item = K.item;
+  v.span_pref = g.seg_span_pref.data();
+  v.span_base = g.seg_span_base.data();
+  v.span_slot = g.seg_span_slot.data();
+  g.n_seg_rows = nrows;
+  g.pr_seg_build_ms = (wall_s() - t0) * 1e3;
+  if (getenv("GRAPEHIP_DEBUG")) {
+    fprintf(stderr,
+            "[pr segments] rows=%lu spans=%lu partials=%lu head=%lu ids=%lu "
+            "item=%u build=%.1fms kept=%.1fMB items:",
+            (unsigned long)nrows, (unsigned long)g.n_seg_spans,
+            (unsigned long)g.n_seg_parts, (unsigned long)K.head,
+            (unsigned long)K.ids, K.item, g.pr_seg_build_ms,
+            (g.n_seg_spans * 24.0 + g.n_seg_parts * 8.0 + nrows * 12.0) / 1e6);
+    for (int k = 0; k < kPrSegs; ++k) fprintf(stderr, " %u", v.n_items[k]);
+    fprintf(stderr, "\n");
+  }
+  g.pr_seg_state = 1;
+  return true;
+}
+
+GpuContext::PrSegDebug GpuContext::debug_pr_segments(DeviceGraph& g) {
+  auto& I = *impl_;
+  hipStream_t s = I.compute;
+  PrSegDebug d;
+  if (world_ > 1 || (g.directed && !g.has_in)) return d;
+  ensure_buckets(g, I, s);
+  d.on = ensure_pr_segments(g, I, s);
+  d.off = (!g.directed ? g.oe_off : g.ie_off).download(s);
+  d.dst = (!g.directed ? g.oe_dst : g.ie_dst).download(s);
+  if (!d.on) return d;
+  d.item = g.seg_view.item;
+  d.bound.assign(g.seg_bound, g.seg_bound + kPrSegs + 1);
+  d.span_first.assign(g.seg_view.span_first,
+                      g.seg_view.span_first + kPrSegs + 1);
+  d.rows = g.seg_rows.download(s);
+  d.span_row = g.seg_span_row.download(s);
+  d.span_slot = g.seg_span_slot.download(s);
+  d.span_pref = g.seg_span_pref.download(s);
+  d.span_base = g.seg_span_base.download(s);
+  d.row_first = g.seg_row_first.download(s);
+  d.build_ms = g.pr_seg_build_ms;
+  d.bytes = g.n_seg_spans * 24 + 8 + g.n_seg_parts * 8 +
+            g.n_seg_rows * 12 + 8;
+  return d;
 }
 
 static void ensure_pr_tiles(DeviceGraph& g, GpuContext::Impl& I,
@@ -4051,6 +4535,9 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
       pull && (te ? atoi(te) != 0 : mean_pull_deg >= 64.0);
   if (want_tiled) ensure_pr_tiles(g, *impl_, s);
   const bool tiled = want_tiled && g.pr_ntiles > 0;
+  // id-segment pull for the mid and hub rows: single-GPU row pull only
+  const bool seg = pull && !multi && !tiled && ensure_pr_segments(g, I, s);
+  if (pull && !multi && !tiled) ++I.pr_path_counts[seg ? 0 : 1];
 
   // working set lives on the DeviceGraph: the cached hipGraph bakes these
   // pointers (locals would dangle across calls — GPU fault under realloc)
@@ -4088,6 +4575,24 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
         pr_pull_small_cm_kernel<P><<<grid_for(g.n_small), kBlock, 0, s>>>(
             pull_off, pull_dst, contrib.data(), g.rows_small.data(),
             g.n_small, g.v_begin, g.v_begin, g.v_end, acc.data());
+      if (seg) {
+        // P == 0 here. Every partial is stored by the pull and read by the
+        // reduce; the kernel boundary carries them across the XCDs.
+        g.seg_ctr.zero(s);
+        const int grid = I.num_cus * kPrSegBlocksPerCu;
+        if (pr_seg_knobs().nt)
+          pr_pull_seg_kernel<true><<<grid, kBlock, 0, s>>>(
+              g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
+              g.seg_part.data());
+        else
+          pr_pull_seg_kernel<false><<<grid, kBlock, 0, s>>>(
+              g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
+              g.seg_part.data());
+        pr_seg_reduce_kernel<<<grid_for(g.n_seg_rows), kBlock, 0, s>>>(
+            g.seg_rows.data(), g.seg_row_first.data(), g.n_seg_rows,
+            g.seg_part.data(), g.v_begin, acc.data());
+        return;
+      }
       if (g.n_mid)
         pr_pull_mid_kernel<P><<<grid_for(g.n_mid * kWave), kBlock, 0, s>>>(
             pull_off, pull_dst, contrib.data(), g.rows_mid.data(), g.n_mid,

@@ -14,6 +14,7 @@
 #include "../core/fragment.hpp"
 #include "../core/net.hpp"
 #include "../core/types.hpp"
+#include "dev_graph.hpp"
 #include "hip_common.hpp"
 
 struct ncclComm;  // fwd (rccl.h included in the .hip TU)
@@ -59,6 +60,21 @@ struct DeviceGraph {
   DeviceBuffer<double> pr_hub_part;
   uint64_t n_hub_items = 0;
   bool buckets_built = false;
+  // PageRank id segments (ensure_pr_segments; layout in dev_graph.hpp).
+  // seg_rows: the mid and hub rows, ascending. Per span, segment-major:
+  // arc prefix, CSR base, index into seg_rows, first partial. A span that
+  // crosses k items owns k consecutive partials; a row's partials are
+  // contiguous in (segment, item) order from seg_row_first[row]. Built once
+  // per graph and alive as long as it (the captured hipGraph bakes the
+  // pointers). pr_seg_state: 0 undecided, 1 built and used, -1 off.
+  DeviceBuffer<uint32_t> seg_rows, seg_span_row, seg_span_slot, seg_ctr;
+  DeviceBuffer<uint64_t> seg_span_pref, seg_span_base, seg_row_first;
+  DeviceBuffer<double> seg_part;
+  uint64_t n_seg_rows = 0, n_seg_spans = 0, n_seg_parts = 0;
+  uint32_t seg_bound[kPrSegs + 1] = {};
+  PrSegView seg_view{};
+  int pr_seg_state = 0;
+  double pr_seg_build_ms = 0;
   // mirror topology (multi-GPU, built lazily): the reference's mirror-info /
   // BatchShuffle design (edgecut_fragment_base.h:569+, cuda batch_shuffle
   // :81-103) recast for xGMI — per-peer sorted lists of the REMOTE vertices
@@ -163,6 +179,23 @@ class GpuContext {
   // order cm, wm, strict, none (host-side count; expand_cm_range is no
   // scheduler choice and is not counted). reset zeroes them after the read.
   std::array<uint64_t, 4> debug_expand_counts(bool reset = false);
+  // test hook: pagerank() calls so far whose mid and hub rows went through
+  // the id-segment pull [0] or the row-tier pulls [1] (single-GPU row pull
+  // only; the tiled and multi-GPU paths count as neither)
+  std::array<uint64_t, 2> debug_pr_path(bool reset = false);
+  // test hook: the id-segment layout of g, built if it is not yet (empty
+  // rows when the path is off for g), with the pull CSR it was cut from
+  struct PrSegDebug {
+    bool on = false;
+    uint32_t item = 0;
+    std::vector<uint32_t> bound, rows, span_row, span_slot;
+    std::vector<uint64_t> span_first, span_pref, span_base, row_first;
+    std::vector<uint64_t> off;
+    std::vector<uint32_t> dst;
+    double build_ms = 0;
+    uint64_t bytes = 0;
+  };
+  PrSegDebug debug_pr_segments(DeviceGraph& g);
   int device_id() const { return dev_; }
   TcpComm* comm() { return comm_; }
   int rank() const { return rank_; }

@@ -384,6 +384,26 @@ PYBIND11_MODULE(_core, m) {
 #endif
            },
            py::arg("reset") = false)
+      .def("_debug_kclique",
+           [](PyEngine& e, bool reset) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (!e.gpu) throw std::runtime_error("no gpu engine");
+             auto c = e.gpu->debug_kclique(reset);
+             py::dict d;
+             d["calls"] = c[0];
+             d["rows_wave"] = c[1];
+             d["rows_block"] = c[2];
+             d["rows_global"] = c[3];
+             d["block_max"] = c[4];
+             d["k_max"] = c[5];
+             return d;
+#else
+             (void)reset;
+             throw std::runtime_error("no hip");
+             return py::dict();
+#endif
+           },
+           py::arg("reset") = false)
       .def("_debug_pr_segments",
            [](PyEngine& e, PyGraph& g) {
 #ifdef GRAPEHIP_WITH_HIP
@@ -1129,6 +1149,23 @@ PYBIND11_MODULE(_core, m) {
            py::arg("graph"), py::arg("source") = 0)
       .def("kclique",
            [](PyEngine& eng, PyGraph& g, int k) {
+#ifdef GRAPEHIP_WITH_HIP
+             // undirected device graphs; above kCliqueMaxK the host path
+             // takes over where there is a host fragment
+             if (eng.use_gpu && g.dev && !g.dev->directed &&
+                 (k <= kCliqueMaxK || !g.frag)) {
+               if (k < 2)
+                 throw std::runtime_error("kclique: k must be >= 2");
+               GpuRunResult r;
+               {
+                 py::gil_scoped_release rel;
+                 r = eng.gpu->kclique(*g.dev, k);
+               }
+               py::dict out = gpu_dict(r, g, /*is_i64=*/true, false);
+               out["clique_count"] = r.count;
+               return out;
+             }
+#endif
              if (!g.frag)
                throw std::runtime_error("kclique needs a host fragment");
              if (k < 2) throw std::runtime_error("kclique: k must be >= 2");

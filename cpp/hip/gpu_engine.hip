@@ -2799,6 +2799,10 @@ struct GpuContext::Impl {
   // pagerank() calls through the id-segment pull [0] and the row-tier
   // pulls [1] (test hook, see debug_pr_path)
   uint64_t pr_path_counts[2] = {0, 0};
+  // device kclique() calls so far, and the rows of the last one in the
+  // wave, block and global tiers (test hook, see debug_kclique)
+  uint64_t kclique_calls = 0;
+  uint64_t kclique_rows[3] = {0, 0, 0};
   int num_cus = 256;  // set by the GpuContext constructor
 };
 
@@ -6721,6 +6725,58 @@ void build_global_csr(GpuContext::Impl& I, int world, uint32_t nv_pad,
                               out.gdst, slice, nv_pad, world, s);
 }
 
+// The degree-oriented CSR of an undirected graph, shared by lcc and kclique:
+// Dv (distinct degree by global index) and O, the deduplicated rows
+// O(v) = {u in N(v) : (D[u], u) > (D[v], v)}, ascending. Multi-GPU holds a
+// PARTIAL oriented CSR: own rows + the remote rows local oriented edges name
+// (reference TransferAdjList staging, cuda/lcc/lcc.h:490-496, recast as a
+// one-shot referenced-row fetch), so memory and exchange volume scale with
+// the boundary, not with V. Fetched rows arrive
+// sorted: owners sort before peers fetch. The caller has ensured the
+// mirrors (multi) and opened its run bracket.
+void build_oriented_csr(GpuContext::Impl& I, TcpComm* comm, DeviceGraph& g,
+                        int rank, int world, DeviceBuffer<uint32_t>& Dv,
+                        GlobalDedupCsr& O, hipStream_t s) {
+  uint32_t nv_pad = padded_nv(g, world);
+  uint32_t owned = g.owned();
+  uint32_t slice = nv_pad / (world ? world : 1);
+  bool multi = world > 1;
+  const uint64_t* off1 = g.oe_off.data();
+  const uint32_t* dst1 = g.oe_dst.data();
+  // referenced-row request lists
+  DeviceBuffer<uint32_t> ridx, sidx;
+  std::vector<uint64_t> roff, soff;
+
+  LccTiers tiers = build_lcc_tiers(I, off1, nullptr, owned, s);
+  lcc_degree_pass(I, g, tiers, off1, dst1, nullptr, nullptr, nv_pad, multi,
+                  Dv, s);
+
+  // oriented adjacency O(v) in capacity layout (cap = D per row)
+  DeviceBuffer<uint32_t> dcap(owned ? owned : 1);
+  HIP_CHECK(hipMemcpyAsync(dcap.data(), Dv.data() + g.v_begin, owned * 4,
+                           hipMemcpyDeviceToDevice, s));
+  CapRows rows = lcc_emit_pass(I, tiers, off1, dst1, nullptr, nullptr, dcap,
+                               true, Dv, owned, g.v_begin, s);
+  // request the rows local oriented edges reference
+  if (multi) {
+    size_t nwords = (static_cast<size_t>(nv_pad) + 31) / 32;
+    DeviceBuffer<uint32_t> bm(nwords);
+    bm.zero(s);
+    if (owned)
+      lcc_mark_oriented_kernel<<<grid_for(static_cast<size_t>(owned) * kWave),
+                                 kBlock, 0, s>>>(
+          rows.ooff.data(), rows.ocnt.data(), rows.oadj.data(), owned,
+          g.v_begin, g.v_end, DevBitmap{bm.data()});
+    build_ref_lists(I, comm, bm, nwords, slice, rank, world, ridx, roff,
+                    sidx, soff, s);
+  }
+  // owners sort their rows before peers fetch them
+  build_global_csr(I, world, nv_pad, slice, owned, g.v_begin, std::move(rows),
+                   true, O, s, multi ? &ridx : nullptr,
+                   multi ? &roff : nullptr, multi ? &sidx : nullptr,
+                   multi ? &soff : nullptr);
+}
+
 // per-vertex open-addressing sets over a global CSR (capacity 2x, pow2)
 void build_hash_sets(GpuContext::Impl& I, uint32_t nv_pad,
                      const GlobalDedupCsr& csr, DeviceBuffer<uint64_t>& hoff,
@@ -6933,59 +6989,17 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
   auto& I = *impl_;
   hipStream_t s = I.compute;
   uint32_t nv_pad = padded_nv(g, world_);
-  uint32_t owned = g.owned();
-  uint32_t slice = nv_pad / (world_ ? world_ : 1);
   bool multi = world_ > 1;
   if (g.directed) return lcc_directed(g, fetch);
 
-  const uint64_t* off1 = g.oe_off.data();
-  const uint32_t* dst1 = g.oe_dst.data();
-
-  // graph-sized working set (freed on return). Multi-GPU holds a PARTIAL
-  // oriented CSR: own rows + the remote rows local oriented edges probe
-  // (reference TransferAdjList staging, cuda/lcc/lcc.h:490-496, recast as
-  // a one-shot referenced-row fetch) — memory and exchange volume scale
-  // with the boundary, not with V.
+  // graph-sized working set (freed on return)
   DeviceBuffer<uint32_t> Dv;  // distinct degree, global idx
   GlobalDedupCsr O;           // oriented CSR (own + referenced rows), sorted
-  // referenced-row request lists
-  DeviceBuffer<uint32_t> ridx, sidx;
-  std::vector<uint64_t> roff, soff;
   if (multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
 
   RunBracket br(I, comm_);
 
-  {
-    LccTiers tiers = build_lcc_tiers(I, off1, nullptr, owned, s);
-    lcc_degree_pass(I, g, tiers, off1, dst1, nullptr, nullptr, nv_pad,
-                      multi, Dv, s);
-
-    // oriented adjacency O(v) in capacity layout (cap = D per row)
-    DeviceBuffer<uint32_t> dcap(owned ? owned : 1);
-    HIP_CHECK(hipMemcpyAsync(dcap.data(), Dv.data() + g.v_begin, owned * 4,
-                             hipMemcpyDeviceToDevice, s));
-    CapRows rows = lcc_emit_pass(I, tiers, off1, dst1, nullptr, nullptr,
-                                 dcap, true, Dv, owned, g.v_begin, s);
-    // request the rows local oriented edges reference
-    if (multi) {
-      size_t nwords = (static_cast<size_t>(nv_pad) + 31) / 32;
-      DeviceBuffer<uint32_t> bm(nwords);
-      bm.zero(s);
-      if (owned)
-        lcc_mark_oriented_kernel<<<grid_for(static_cast<size_t>(owned) *
-                                            kWave),
-                                   kBlock, 0, s>>>(
-            rows.ooff.data(), rows.ocnt.data(), rows.oadj.data(), owned,
-            g.v_begin, g.v_end, DevBitmap{bm.data()});
-      build_ref_lists(I, comm_, bm, nwords, slice, rank_, world_, ridx, roff,
-                      sidx, soff, s);
-    }
-    // owners sort their rows before peers fetch them
-    build_global_csr(I, world_, nv_pad, slice, owned, g.v_begin,
-                     std::move(rows), true, O, s, multi ? &ridx : nullptr,
-                     multi ? &roff : nullptr, multi ? &sidx : nullptr,
-                     multi ? &soff : nullptr);
-  }
+  build_oriented_csr(I, comm_, g, rank_, world_, Dv, O, s);
 
   // per-vertex oriented hash sets (intersection via O(1) probes)
   DeviceBuffer<uint64_t> hoff;
@@ -7018,6 +7032,445 @@ GpuRunResult GpuContext::lcc(DeviceGraph& g, bool fetch) {
         t.heavy_q.data(), hn, t.Tcnt.data());
   if (multi) I.dc.allreduce_sum_u64(t.Tcnt.data(), nv_pad, s);
   return lcc_finish(br, g, t, Dv, 2.0, fetch, s);
+}
+
+// ---------------------------------------------------------------------------
+// k-clique counting: bitmap enumeration over the oriented CSR (KERNELS.md
+// "k-clique bitmap enumeration"). Every vertex of a clique rooted at an owned
+// v (its lowest vertex in (D, id) order) lies in O(v), so per row the induced
+// DAG on O(v) = u_0..u_{d-1} is a d x ceil(d/64) bit matrix, bit (i, j) set
+// iff u_j is in O(u_i), and the (k-1)-cliques of that DAG are counted by
+// bitset recursion: cand_1 = adj[i], cand_{t+1} = cand_t & adj[j] for each
+// j in cand_t, popc(cand) once k-1 vertices are fixed. The orientation is
+// acyclic, so each clique is met once.
+// ---------------------------------------------------------------------------
+
+#ifndef GRAPEHIP_KCLIQUE_BLOCK_MAX
+#define GRAPEHIP_KCLIQUE_BLOCK_MAX 512
+#endif
+// Largest d whose matrix is staged in LDS, one block per row: 512^2 bits are
+// 32 KiB (four blocks per CU), 1024^2 bits 128 KiB (one). Measured in
+// profiles/r10_gpu_kclique.md.
+constexpr uint32_t kCliqueBlockMax = GRAPEHIP_KCLIQUE_BLOCK_MAX;
+static_assert(kCliqueBlockMax >= 128 && kCliqueBlockMax <= 1024 &&
+                  kCliqueBlockMax % 64 == 0,
+              "block tier: 2 to 16 mask words per row");
+// global tier: one wave per DFS, up to 16 mask words per lane
+constexpr uint32_t kCliqueMaxWpl = 16;
+constexpr uint32_t kCliqueMaxDeg = kWave * 64 * kCliqueMaxWpl;  // 65536
+// HBM workspace of the global tier: at most this, or one slab if larger
+constexpr uint64_t kCliqueWorkspaceBytes = 1ull << 30;
+constexpr int kCliqueGlobalBlocksPerCu = 2;
+constexpr uint32_t kCliqueNone = 0xFFFFFFFFu;
+
+// one candidate set, spread over a group of G lanes: lane l of the group
+// holds words l, l + G, l + 2G, ...
+template <int WPL>
+struct KcMask {
+  unsigned long long w[WPL];
+};
+
+// lowest member of the group's set above `prev` (-1: lowest of all), the
+// same value in every lane of the group; kCliqueNone when there is none.
+// All lanes of a group call this together.
+template <int G, int WPL>
+__device__ __forceinline__ uint32_t kc_next(const KcMask<WPL>& c,
+                                            uint32_t lane_g, int prev) {
+  const int pw = prev >> 6;  // -1 for prev == -1
+  const int pb = prev & 63;
+  uint32_t mine = kCliqueNone;
+#pragma unroll
+  for (int q = WPL - 1; q >= 0; --q) {  // descending: the lowest word wins
+    const int wi = static_cast<int>(lane_g) + G * q;
+    unsigned long long x = c.w[q];
+    if (wi < pw)
+      x = 0;
+    else if (wi == pw)
+      x = pb == 63 ? 0ull : x & (~0ull << (pb + 1));
+    if (x) mine = static_cast<uint32_t>(wi) * 64 + (__ffsll(x) - 1);
+  }
+#pragma unroll
+  for (int o = G / 2; o > 0; o >>= 1) {
+    uint32_t other = __shfl_xor(mine, o, 64);
+    mine = other < mine ? other : mine;
+  }
+  return mine;
+}
+
+// Cliques below `cand` with `need` more vertices to fix before the leaf;
+// each lane returns the share of its own words. LEFT bounds the recursion at
+// compile time, so the mask stack lives in registers.
+template <int G, int WPL, int LEFT>
+__device__ __forceinline__ unsigned long long kc_dfs(
+    const unsigned long long* adj, uint32_t W, uint32_t lane_g,
+    const KcMask<WPL>& cand, int need) {
+  unsigned long long t = 0;
+  if (need == 0) {
+#pragma unroll
+    for (int q = 0; q < WPL; ++q) t += __popcll(cand.w[q]);
+    return t;
+  }
+  if constexpr (LEFT > 0) {
+    int prev = -1;
+    for (;;) {
+      uint32_t j = kc_next<G, WPL>(cand, lane_g, prev);
+      if (j == kCliqueNone) break;
+      prev = static_cast<int>(j);
+      const unsigned long long* row = adj + static_cast<size_t>(j) * W;
+      KcMask<WPL> nxt;
+#pragma unroll
+      for (int q = 0; q < WPL; ++q) {
+        uint32_t wi = lane_g + G * q;
+        nxt.w[q] = wi < W ? cand.w[q] & row[wi] : 0ull;
+      }
+      t += kc_dfs<G, WPL, LEFT - 1>(adj, W, lane_g, nxt, need - 1);
+    }
+  }
+  return t;
+}
+
+// The groups of a block take the sub-roots i of one row from a shared
+// counter (balance: the subtrees differ widely); each runs the DFS below
+// cand_1 = adj[i].
+template <int G, int WPL>
+__device__ __forceinline__ unsigned long long kc_group_roots(
+    const unsigned long long* adj, uint32_t d, uint32_t W, uint32_t* next,
+    int need) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t lane_g = lane & (G - 1);
+  unsigned long long t = 0;
+  for (;;) {
+    uint32_t i = 0;
+    if (lane_g == 0) i = atomicAdd(next, 1u);
+    i = __shfl(i, static_cast<int>(lane - lane_g), 64);
+    if (i >= d) break;
+    const unsigned long long* row = adj + static_cast<size_t>(i) * W;
+    KcMask<WPL> cand;
+#pragma unroll
+    for (int q = 0; q < WPL; ++q) {
+      uint32_t wi = lane_g + G * q;
+      cand.w[q] = wi < W ? row[wi] : 0ull;
+    }
+    t += kc_dfs<G, WPL, kCliqueMaxK - 3>(adj, W, lane_g, cand, need);
+  }
+  return t;
+}
+
+// bit (i, j) for every w = u_j of O(u_i) found in the sorted nbr[0..d): the
+// block's waves stride the rows i, the lanes of a wave the entries of O(u_i).
+// adj is zeroed and the writes are visible to the block.
+__device__ __forceinline__ void kc_build_matrix(
+    const uint64_t* __restrict__ goff, const uint32_t* __restrict__ gdst,
+    const uint32_t* nbr, uint32_t d, uint32_t W, unsigned long long* adj) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wpb = blockDim.x >> 6;
+  for (uint32_t i = threadIdx.x >> 6; i < d; i += wpb) {
+    uint32_t u = nbr[i];
+    uint64_t ub = goff[u];
+    uint32_t un = static_cast<uint32_t>(goff[u + 1] - ub);
+    for (uint32_t e = lane; e < un; e += kWave) {
+      uint32_t w = gdst[ub + e];
+      uint32_t lo = 0, hi = d;
+      while (lo < hi) {
+        uint32_t mid = (lo + hi) >> 1;
+        if (nbr[mid] < w)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      if (lo < d && nbr[lo] == w)
+        atomicOr(&adj[static_cast<size_t>(i) * W + (lo >> 6)],
+                 1ull << (lo & 63));
+    }
+  }
+}
+
+__device__ __forceinline__ void kc_add_total(unsigned long long t,
+                                             unsigned long long* total) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
+  if ((threadIdx.x & 63) == 0 && t) atomicAdd(total, t);
+}
+
+// wave tier (d <= 64): one wave per row, lane i owns u_i and matrix row i.
+// Row i is one ballot: lane j searches u_j in the sorted O(u_i). The words
+// are parked in LDS per wave for the DFS, where lane i walks the subtree of
+// sub-root i alone (G = 1: no cross-lane traffic).
+__global__ __launch_bounds__(kBlock) void kclique_wave_kernel(
+    const uint64_t* __restrict__ goff, const uint32_t* __restrict__ gdst,
+    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
+    int need, unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long s_adj[kBlock / kWave][kWave];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t wid = threadIdx.x >> 6;
+  const uint32_t wpb = kBlock / kWave;
+  unsigned long long* adj = s_adj[wid];
+  size_t wstride = static_cast<size_t>(gridDim.x) * wpb;
+  unsigned long long t = 0;
+  for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * wpb + wid; r < nrows;
+       r += wstride) {
+    uint32_t v = v_begin + rows[r];
+    uint64_t vb = goff[v];
+    uint32_t d = static_cast<uint32_t>(goff[v + 1] - vb);  // <= 64
+    uint32_t mine = lane < d ? gdst[vb + lane] : 0;
+    unsigned long long my_row = 0;
+    for (uint32_t i = 0; i < d; ++i) {
+      uint32_t u = __shfl(mine, static_cast<int>(i), 64);
+      uint64_t ub = goff[u];
+      uint32_t lo = 0, hi = static_cast<uint32_t>(goff[u + 1] - ub);
+      const uint32_t un = hi;
+      bool hit = false;
+      if (lane < d) {
+        while (lo < hi) {
+          uint32_t mid = (lo + hi) >> 1;
+          if (gdst[ub + mid] < mine)
+            lo = mid + 1;
+          else
+            hi = mid;
+        }
+        hit = lo < un && gdst[ub + lo] == mine;
+      }
+      unsigned long long word = __ballot(hit);
+      if (lane == i) my_row = word;
+    }
+    // the wave's own LDS traffic is ordered; the fences keep the compiler
+    // from moving the DFS reads above the store (and the next row's store
+    // above this row's reads)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    adj[lane] = my_row;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    if (lane < d) {
+      KcMask<1> cand{{my_row}};
+      t += kc_dfs<1, 1, kCliqueMaxK - 3>(adj, 1, 0, cand, need);
+    }
+  }
+  kc_add_total(t, total);
+}
+
+// block tier (64 < d <= kCliqueBlockMax): one block per row, O(v) and the
+// matrix staged in LDS, the matrix built with LDS atomicOr. Groups of G =
+// W rounded up to a power of two lanes own one DFS each, one word per lane.
+__global__ __launch_bounds__(kBlock) void kclique_block_kernel(
+    const uint64_t* __restrict__ goff, const uint32_t* __restrict__ gdst,
+    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
+    int need, unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long s_adj[kCliqueBlockMax * (kCliqueBlockMax / 64)];
+  __shared__ uint32_t s_nbr[kCliqueBlockMax];
+  __shared__ uint32_t s_next;
+  unsigned long long t = 0;
+  for (uint64_t r = blockIdx.x; r < nrows; r += gridDim.x) {
+    uint32_t v = v_begin + rows[r];
+    uint64_t vb = goff[v];
+    uint32_t d = static_cast<uint32_t>(goff[v + 1] - vb);
+    uint32_t W = (d + 63) >> 6;  // 2..kCliqueBlockMax/64
+    for (uint32_t x = threadIdx.x; x < d; x += blockDim.x)
+      s_nbr[x] = gdst[vb + x];
+    for (uint32_t x = threadIdx.x; x < d * W; x += blockDim.x) s_adj[x] = 0;
+    if (threadIdx.x == 0) s_next = 0;
+    __syncthreads();
+    kc_build_matrix(goff, gdst, s_nbr, d, W, s_adj);
+    __syncthreads();
+    if (W <= 2)
+      t += kc_group_roots<2, 1>(s_adj, d, W, &s_next, need);
+    else if (W <= 4)
+      t += kc_group_roots<4, 1>(s_adj, d, W, &s_next, need);
+    else if (W <= 8)
+      t += kc_group_roots<8, 1>(s_adj, d, W, &s_next, need);
+    else
+      t += kc_group_roots<16, 1>(s_adj, d, W, &s_next, need);
+    __syncthreads();
+  }
+  kc_add_total(t, total);
+}
+
+// global tier (d > kCliqueBlockMax): persistent blocks, the matrix of the
+// row in hand in the block's HBM slab (slab_words, sized by the largest d of
+// the tier), O(v) searched where it lies in the CSR. One wave per DFS, WPL
+// words per lane (64 * WPL >= W for every row of the tier). The slab is
+// reused from row to row and the matrix is written with device atomics, so
+// agent-scope fences around the barriers keep a wave from reading the last
+// row's lines out of its L1.
+template <int WPL>
+__global__ __launch_bounds__(kBlock) void kclique_global_kernel(
+    const uint64_t* __restrict__ goff, const uint32_t* __restrict__ gdst,
+    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t v_begin,
+    int need, unsigned long long* ws, uint64_t slab_words,
+    unsigned long long* __restrict__ total) {
+  __shared__ uint32_t s_next;
+  unsigned long long* adj = ws + static_cast<size_t>(blockIdx.x) * slab_words;
+  unsigned long long t = 0;
+  for (uint64_t r = blockIdx.x; r < nrows; r += gridDim.x) {
+    uint32_t v = v_begin + rows[r];
+    uint64_t vb = goff[v];
+    uint32_t d = static_cast<uint32_t>(goff[v + 1] - vb);
+    uint32_t W = (d + 63) >> 6;
+    const uint64_t words = static_cast<uint64_t>(d) * W;  // <= slab_words
+    for (uint64_t x = threadIdx.x; x < words; x += blockDim.x) adj[x] = 0;
+    if (threadIdx.x == 0) s_next = 0;
+    __threadfence();
+    __syncthreads();
+    kc_build_matrix(goff, gdst, gdst + vb, d, W, adj);
+    __threadfence();
+    __syncthreads();
+    __threadfence();
+    t += kc_group_roots<kWave, WPL>(adj, d, W, &s_next, need);
+    __syncthreads();
+  }
+  kc_add_total(t, total);
+}
+
+namespace {
+
+// rows by oriented out-degree d; rows with d < k - 1 root no k-clique
+struct KCliqueTiers {
+  static constexpr int kLists = 3, kBins = 3;
+  const uint64_t* __restrict__ goff;
+  uint32_t v_begin, min_d;
+  __device__ __forceinline__ int operator()(uint32_t r) const {
+    uint64_t d = goff[v_begin + r + 1] - goff[v_begin + r];
+    return d < min_d ? -1 : (d <= kWave ? 0 : (d <= kCliqueBlockMax ? 1 : 2));
+  }
+};
+
+__global__ void kclique_maxlen_kernel(const uint64_t* __restrict__ goff,
+                                      const uint32_t* __restrict__ rows,
+                                      uint64_t nrows, uint32_t v_begin,
+                                      uint32_t* __restrict__ out) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = blockIdx.x * blockDim.x + threadIdx.x; i < nrows;
+       i += stride) {
+    uint32_t v = v_begin + rows[i];
+    uint64_t d = goff[v + 1] - goff[v];
+    atomicMax(out, static_cast<uint32_t>(
+                       d < 0xFFFFFFFFull ? d : 0xFFFFFFFFull));
+  }
+}
+
+template <int WPL>
+void launch_kclique_global(int grid, hipStream_t s, const GlobalDedupCsr& O,
+                           const uint32_t* rows, uint64_t nrows,
+                           uint32_t v_begin, int need,
+                           unsigned long long* ws, uint64_t slab_words,
+                           unsigned long long* total) {
+  kclique_global_kernel<WPL><<<grid, kBlock, 0, s>>>(
+      O.goff.data(), O.gdst.data(), rows, nrows, v_begin, need, ws,
+      slab_words, total);
+}
+
+}  // namespace
+
+GpuRunResult GpuContext::kclique(DeviceGraph& g, int k) {
+  RangeMarker _mk("grapehip::kclique");
+  auto& I = *impl_;
+  hipStream_t s = I.compute;
+  if (g.directed)
+    throw std::runtime_error("GPU kclique: undirected graphs only");
+  if (k < 2) throw std::runtime_error("kclique: k must be >= 2");
+  if (k > kCliqueMaxK)
+    throw std::runtime_error("kclique: k = " + std::to_string(k) +
+                             " is above the device limit of " +
+                             std::to_string(kCliqueMaxK) + " (kCliqueMaxK)");
+  uint32_t nv_pad = padded_nv(g, world_);
+  uint32_t owned = g.owned();
+  bool multi = world_ > 1;
+
+  // graph-sized working set (freed on return)
+  DeviceBuffer<uint32_t> Dv;
+  GlobalDedupCsr O;
+  if (multi) ensure_mirrors(I, comm_, g, rank_, world_, s);
+
+  RunBracket br(I, comm_);
+
+  build_oriented_csr(I, comm_, g, rank_, world_, Dv, O, s);
+  Dv.free();
+
+  DeviceBuffer<unsigned long long> total(1);
+  total.zero(s);
+  uint64_t n_tier[3] = {0, 0, 0};
+  if (k == 2) {
+    // the oriented arcs of the owned rows
+    uint64_t lo = 0, hi = 0;
+    HIP_CHECK(hipMemcpyAsync(&lo, O.goff.data() + g.v_begin, 8,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(
+        &hi, O.goff.data() + std::min<uint64_t>(g.v_end, nv_pad), 8,
+        hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    unsigned long long arcs = hi - lo;
+    HIP_CHECK(hipMemcpyAsync(total.data(), &arcs, 8, hipMemcpyHostToDevice,
+                             s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  } else if (owned) {
+    const int need = k - 3;  // v and the sub-root are fixed
+    DeviceBuffer<uint32_t> wave_rows, block_rows, global_rows;
+    auto tc = partition_rows(
+        KCliqueTiers{O.goff.data(), g.v_begin, static_cast<uint32_t>(k - 1)},
+        owned, {&wave_rows, &block_rows, &global_rows}, s);
+    for (int b = 0; b < 3; ++b) n_tier[b] = tc[b];
+    // the heaviest rows first in flight, the many light ones fill in
+    DeviceBuffer<unsigned long long> ws;
+    if (n_tier[2]) {
+      DeviceBuffer<uint32_t> dmax(1);
+      dmax.zero(s);
+      kclique_maxlen_kernel<<<grid_for(n_tier[2]), kBlock, 0, s>>>(
+          O.goff.data(), global_rows.data(), n_tier[2], g.v_begin,
+          dmax.data());
+      uint32_t d_max = dmax.download(s)[0];
+      if (d_max > kCliqueMaxDeg)
+        throw std::runtime_error(
+            "kclique: an oriented row of " + std::to_string(d_max) +
+            " entries is above the device limit of " +
+            std::to_string(kCliqueMaxDeg));
+      const uint32_t w_max = (d_max + 63) / 64;
+      const uint64_t slab_words = static_cast<uint64_t>(d_max) * w_max;
+      uint64_t grid = std::max<uint64_t>(
+          1, kCliqueWorkspaceBytes / (slab_words * 8));
+      grid = std::min<uint64_t>(
+          grid, static_cast<uint64_t>(I.num_cus) * kCliqueGlobalBlocksPerCu);
+      grid = std::min<uint64_t>(grid, n_tier[2]);
+      ws.resize(grid * slab_words);
+      const uint32_t wpl = (w_max + kWave - 1) / kWave;
+      auto launch = wpl <= 1   ? launch_kclique_global<1>
+                    : wpl <= 2 ? launch_kclique_global<2>
+                    : wpl <= 4 ? launch_kclique_global<4>
+                    : wpl <= 8 ? launch_kclique_global<8>
+                               : launch_kclique_global<16>;
+      launch(static_cast<int>(grid), s, O, global_rows.data(), n_tier[2],
+             g.v_begin, need, ws.data(), slab_words, total.data());
+    }
+    if (n_tier[1])
+      kclique_block_kernel<<<std::min<uint64_t>(n_tier[1], kMaxGrid), kBlock,
+                             0, s>>>(O.goff.data(), O.gdst.data(),
+                                     block_rows.data(), n_tier[1], g.v_begin,
+                                     need, total.data());
+    if (n_tier[0])
+      kclique_wave_kernel<<<grid_for(n_tier[0] * kWave), kBlock, 0, s>>>(
+          O.goff.data(), O.gdst.data(), wave_rows.data(), n_tier[0],
+          g.v_begin, need, total.data());
+    HIP_CHECK(hipStreamSynchronize(s));  // the row lists go out of scope
+  }
+  if (multi) I.dc.allreduce_sum_u64(total.data(), 1, s);
+  uint64_t count = total.download(s)[0];
+  ++I.kclique_calls;
+  for (int b = 0; b < 3; ++b) I.kclique_rows[b] = n_tier[b];
+  GpuRunResult res = br.finish(1, g.input_edges);
+  res.count = count;
+  return res;
+}
+
+std::array<uint64_t, 6> GpuContext::debug_kclique(bool reset) {
+  auto& I = *impl_;
+  std::array<uint64_t, 6> out = {I.kclique_calls, I.kclique_rows[0],
+                                 I.kclique_rows[1], I.kclique_rows[2],
+                                 kCliqueBlockMax,
+                                 static_cast<uint64_t>(kCliqueMaxK)};
+  if (reset) {
+    I.kclique_calls = 0;
+    for (auto& r : I.kclique_rows) r = 0;
+  }
+  return out;
 }
 
 }  // namespace grapehip

@@ -128,7 +128,11 @@ struct GpuRunResult {
   // this rank's data-plane sends during the run (comm-volume evidence:
   // p2p halo/mirror/row-fetch vs collective traffic)
   uint64_t bytes_p2p = 0, bytes_coll = 0;
+  uint64_t count = 0;  // kclique: the global number of k-cliques
 };
+
+// largest k of the device kclique (its mask stack is k - 2 registers deep)
+constexpr int kCliqueMaxK = 8;
 
 class GpuContext {
  public:
@@ -165,6 +169,10 @@ class GpuContext {
   // single-source Brandes on the stored out-CSR (cpp/apps/bc.hpp semantics)
   // f64: dependency delta, f64b: path counts, i64: depth; rounds: levels
   GpuRunResult bc(DeviceGraph& g, int64_t source, bool fetch = true);
+  // k-cliques of an undirected graph, 2 <= k <= kCliqueMaxK, by bitmap
+  // enumeration over the degree-oriented CSR; count: the global total on
+  // every rank
+  GpuRunResult kclique(DeviceGraph& g, int k);
 
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device
@@ -183,6 +191,10 @@ class GpuContext {
   // the id-segment pull [0] or the row-tier pulls [1] (single-GPU row pull
   // only; the tiled and multi-GPU paths count as neither)
   std::array<uint64_t, 2> debug_pr_path(bool reset = false);
+  // test hook: device kclique() calls so far, the rows of the last call in
+  // the wave, block and global tiers, kCliqueBlockMax and kCliqueMaxK, in
+  // that order. reset zeroes the first four after the read.
+  std::array<uint64_t, 6> debug_kclique(bool reset = false);
   // test hook: the id-segment layout of g, built if it is not yet (empty
   // rows when the path is off for g), with the pull CSR it was cut from
   struct PrSegDebug {

@@ -10,6 +10,7 @@ ap.add_argument("--apps", default="bfs,sssp,pagerank,wcc,cdlp,lcc,kcore,"
                                   "core_decomposition")
 ap.add_argument("--cdlp-iters", type=int, default=10)
 ap.add_argument("--kcore-k", type=int, default=3)
+ap.add_argument("--kclique-k", type=int, default=3)
 ap.add_argument("--repeat", type=int, default=1,
                 help="timed runs per app; above 1 every time is also "
                      "listed under <app>_ms_all")
@@ -44,6 +45,8 @@ def run_app(app):
         return eng.core_decomposition(g, values=False)
     if app == "bc":  # not in the default list
         return eng.bc(g, 0, values=False)
+    if app == "kclique":  # not in the default list; undirected graphs
+        return eng.kclique(g, args.kclique_k)
     raise SystemExit("unknown app " + app)
 
 
@@ -75,4 +78,7 @@ for app in args.apps.split(","):
         out[app + "_ms_all"] = [round(t * 1e3, 2) for t in times]
     out[app + "_ms"] = round(r["seconds"] * 1e3, 2)
     out[app + "_rounds"] = r["rounds"]
+    if app == "kclique":
+        out["kclique_k"] = args.kclique_k
+        out["kclique_count"] = int(r["clique_count"])
 print(json.dumps(out))

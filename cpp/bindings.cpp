@@ -404,6 +404,29 @@ PYBIND11_MODULE(_core, m) {
 #endif
            },
            py::arg("reset") = false)
+      .def("_debug_sample",
+           [](PyEngine& e, bool reset) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (!e.gpu) throw std::runtime_error("no gpu engine");
+             auto c = e.gpu->debug_sample(reset);
+             py::dict d;
+             d["calls"] = c.calls;
+             d["cdf_builds"] = c.cdf_builds;
+             d["topk_builds"] = c.topk_builds;
+             d["steps"] = c.steps;
+             d["cdf_bytes"] = c.cdf_bytes;
+             d["topk_bytes"] = c.topk_bytes;
+             d["cdf_ms"] = c.cdf_ms;
+             d["topk_ms"] = c.topk_ms;
+             d["top_k_max"] = kSampleTopKMax;
+             return d;
+#else
+             (void)reset;
+             throw std::runtime_error("no hip");
+             return py::dict();
+#endif
+           },
+           py::arg("reset") = false)
       .def("_debug_pr_segments",
            [](PyEngine& e, PyGraph& g) {
 #ifdef GRAPEHIP_WITH_HIP
@@ -1074,8 +1097,18 @@ PYBIND11_MODULE(_core, m) {
            py::arg("iters") = 10)
       .def("sample",
            [](PyEngine& eng, PyGraph& g, arr_i64 starts, int hops,
-              const std::string& strategy, int top_k, uint64_t seed) {
-             if (!g.frag)
+              const std::string& strategy, int top_k, uint64_t seed,
+              std::optional<bool> device) {
+             // device unset: the host app wherever it can run (its results
+             // for a seed stay what they were), the device otherwise
+             bool on_device = device.has_value() ? *device : !g.frag;
+#ifdef GRAPEHIP_WITH_HIP
+             if (!device.has_value() && !(eng.use_gpu && g.dev))
+               on_device = false;
+#else
+             if (!device.has_value()) on_device = false;
+#endif
+             if (!on_device && !g.frag)
                throw std::runtime_error("sample needs a host fragment");
              SampleStrategy st;
              if (strategy == "random")
@@ -1087,6 +1120,51 @@ PYBIND11_MODULE(_core, m) {
              else
                throw std::runtime_error(
                    "strategy must be random|edge_weight|top_k");
+             if (on_device) {
+#ifdef GRAPEHIP_WITH_HIP
+               if (!eng.use_gpu || !eng.gpu)
+                 throw std::runtime_error(
+                     "sample(device=True) needs an engine with gpu=True");
+               if (!g.dev)
+                 throw std::runtime_error(
+                     "sample(device=True): the graph has no device graph");
+               DevIdMap m = dev_id_map(g);
+               std::vector<uint32_t> dev_starts(starts.size());
+               for (ssize_t i = 0; i < starts.size(); ++i) {
+                 int64_t oid = starts.data()[i];
+                 uint32_t v = kSampleNoVertex;
+                 vid_t gid;
+                 if (!m.frag) {
+                   if (oid >= 0 &&
+                       static_cast<uint64_t>(oid) < g.dev->nv_real)
+                     v = static_cast<uint32_t>(oid);
+                 } else if (m.frag->vm().get_gid(oid, &gid)) {
+                   v = m.to_dev(oid);
+                 }
+                 dev_starts[i] = v;
+               }
+               GpuRunResult r;
+               {
+                 py::gil_scoped_release rel;
+                 r = eng.gpu->sample(*g.dev, dev_starts, hops,
+                                     static_cast<int>(st), top_k, seed);
+               }
+               py::dict out = gpu_dict(r, g, /*is_i64=*/true, false);
+               size_t n = r.walk_ids.size(), len = hops + 1;
+               py::array_t<int64_t> paths({n, len});
+               auto* pp = paths.mutable_data();
+               for (size_t i = 0; i < n * len; ++i)
+                 pp[i] = r.paths[i] == kSampleNoVertex
+                             ? -1
+                             : m.to_oid(r.paths[i]);
+               out["walk_ids"] = to_np(r.walk_ids);
+               out["paths"] = paths;
+               return out;
+#else
+               throw std::runtime_error(
+                   "sample(device=True): built without HIP");
+#endif
+             }
              std::vector<oid_t> st_oids(starts.data(),
                                         starts.data() + starts.size());
              SamplerApp app;
@@ -1127,7 +1205,7 @@ PYBIND11_MODULE(_core, m) {
            },
            py::arg("graph"), py::arg("starts"), py::arg("hops") = 2,
            py::arg("strategy") = "random", py::arg("top_k") = 4,
-           py::arg("seed") = 7)
+           py::arg("seed") = 7, py::arg("device") = std::nullopt)
       .def("sssp_auto",
            [](PyEngine& eng, PyGraph& g, int64_t source) {
              if (!g.frag)

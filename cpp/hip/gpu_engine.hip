@@ -2803,6 +2803,13 @@ struct GpuContext::Impl {
   // wave, block and global tiers (test hook, see debug_kclique)
   uint64_t kclique_calls = 0;
   uint64_t kclique_rows[3] = {0, 0, 0};
+  // sample() workspace, grow-only like the traversal buffers: the two
+  // walker queues and the per-peer send regions (8 B per walk each, the
+  // regions per peer), the path table (4 B per walk and hop), the counters
+  // and the start / owned-walk / result staging
+  DeviceBuffer<unsigned long long> sample_q[2], sample_peer, sample_cnt;
+  DeviceBuffer<uint32_t> sample_paths, sample_starts, sample_own, sample_out;
+  GpuContext::SampleDebug sample_dbg;  // test hook, see debug_sample
   int num_cus = 256;  // set by the GpuContext constructor
 };
 
@@ -7470,6 +7477,711 @@ std::array<uint64_t, 6> GpuContext::debug_kclique(bool reset) {
     I.kclique_calls = 0;
     for (auto& r : I.kclique_rows) r = 0;
   }
+  return out;
+}
+
+}  // namespace grapehip
+
+namespace grapehip {
+
+// ===========================================================================
+// Random-walk sampler (cpp/apps/sampler.hpp on the device). Reference parity:
+// examples/gnn_sampler/sampler.h strategies random / edge_weight / top_k
+// with per-vertex indexes (fragment_indices.h), recast as walker queues.
+//
+// One 64-bit draw per step, a function of (seed, walk, hop) alone, so a path
+// does not depend on which rank takes the step. A row is the stored out-row
+// of the vertex (ascending device id), deg its length:
+//   random       pick = hi64(r * deg)
+//   edge_weight  cdf = inclusive fp32 prefix sum of the row's weights,
+//                t = fp32(r >> 40) * 2^-24 * cdf[deg - 1] (one fp32 multiply),
+//                pick = min(deg - 1, #{i : cdf[i] <= t}); a row whose total
+//                is not > 0 is a dead end
+//   top_k        kk = min(k, deg), pick = the hi64(r * kk)-th arc of the row
+//                ordered by weight descending, ties to the smaller slot
+// An unweighted graph has every weight 1: edge_weight is then random and
+// top_k draws among the first kk slots, with no index.
+//
+// Walkers are (vertex, walk) pairs in a queue; a step kernel handles one
+// walker per lane, writes paths[walk][hop + 1] and appends the walker to the
+// next queue (vertex owned) or to the owner's send region, one atomic per
+// wave and target. Several ranks: the regions go out with DevComm::sendrecv
+// straight into the tail of the receiver's next queue, lengths on the
+// control plane; walkers are not deduplicated (two walks may sit on one
+// vertex). Every path slot is written by at most one rank over 0xFFFFFFFF,
+// so an element-wise min over ranks completes the table at the end.
+// ===========================================================================
+
+constexpr uint32_t kSampleThreadDeg = 8;   // thread-per-row index builds
+constexpr uint32_t kSampleWaveDeg = 1024;  // wave-per-row; longer: a block
+constexpr int kSampleWaveKeys = kSampleWaveDeg / kWave;
+
+struct SampleWalker {
+  uint32_t v, walk;
+};
+static_assert(sizeof(SampleWalker) == 8, "walker queues hold 8-byte entries");
+
+// index-build tiers by row length d: rows of at most min_d arcs have no
+// index entry
+struct SampleLenTiers {
+  static constexpr int kLists = 3, kBins = 3;
+  const uint64_t* __restrict__ off;
+  uint32_t min_d;
+  __device__ __forceinline__ int operator()(uint32_t r) const {
+    uint64_t d = off[r + 1] - off[r];
+    return d <= min_d ? -1
+                      : (d <= kSampleThreadDeg ? 0
+                                               : (d <= kSampleWaveDeg ? 1 : 2));
+  }
+};
+
+__device__ __forceinline__ uint64_t sample_draw(uint64_t seed, uint64_t walk,
+                                                uint64_t hop) {
+  uint64_t x = seed * 0x9E3779B97F4A7C15ULL + walk * 0xD1B54A32D192ED03ULL +
+               hop;
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ULL;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBULL;
+  return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ float wave_incl_scan_f32(float v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    float up = __shfl_up(v, d, 64);
+    if (lane >= d) v += up;
+  }
+  return v;
+}
+
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    uint64_t o = __shfl_xor(static_cast<unsigned long long>(v), d, 64);
+    if (o > v) v = o;
+  }
+  return v;
+}
+
+// --- cdf index: segmented inclusive scan of the weights, three tiers --------
+
+__global__ void sample_cdf_thread_kernel(const uint64_t* __restrict__ off,
+                                         const float* __restrict__ w,
+                                         const uint32_t* __restrict__ rows,
+                                         uint64_t nrows,
+                                         float* __restrict__ cdf) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < nrows; i += stride) {
+    uint32_t r = rows[i];
+    float acc = 0.f;
+    for (uint64_t e = off[r]; e < off[r + 1]; ++e) {
+      acc += w[e];
+      cdf[e] = acc;
+    }
+  }
+}
+
+__global__ void sample_cdf_wave_kernel(const uint64_t* __restrict__ off,
+                                       const float* __restrict__ w,
+                                       const uint32_t* __restrict__ rows,
+                                       uint64_t nrows,
+                                       float* __restrict__ cdf) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t nwaves = (static_cast<uint64_t>(gridDim.x) * blockDim.x) >> 6;
+  for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                     threadIdx.x) >> 6;
+       i < nrows; i += nwaves) {
+    uint32_t r = rows[i];
+    const uint64_t b = off[r], e = off[r + 1];
+    float carry = 0.f;
+    for (uint64_t base = b; base < e; base += kWave) {
+      uint64_t idx = base + lane;
+      float s = wave_incl_scan_f32(idx < e ? w[idx] : 0.f);
+      if (idx < e) cdf[idx] = carry + s;
+      carry += __shfl(s, 63, 64);
+    }
+  }
+}
+
+// hub rows: a block scans kBlock arcs at a time and carries the running
+// total from chunk to chunk
+__global__ void __launch_bounds__(kBlock)
+sample_cdf_block_kernel(const uint64_t* __restrict__ off,
+                        const float* __restrict__ w,
+                        const uint32_t* __restrict__ rows, uint64_t nrows,
+                        float* __restrict__ cdf) {
+  __shared__ float s_wave[kBlock / kWave];
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
+    uint32_t r = rows[i];
+    const uint64_t b = off[r], e = off[r + 1];
+    float carry = 0.f;
+    for (uint64_t base = b; base < e; base += kBlock) {
+      uint64_t idx = base + threadIdx.x;
+      float s = wave_incl_scan_f32(idx < e ? w[idx] : 0.f);
+      if (lane == 63) s_wave[wid] = s;
+      __syncthreads();
+      float before = 0.f, total = 0.f;
+#pragma unroll
+      for (uint32_t q = 0; q < kBlock / kWave; ++q) {
+        if (q < wid) before += s_wave[q];
+        total += s_wave[q];
+      }
+      if (idx < e) cdf[idx] = carry + (before + s);
+      carry += total;
+      __syncthreads();
+    }
+  }
+}
+
+// --- top-k index: k arg-max passes under (weight, -slot), three tiers -------
+
+// larger key = earlier in the order: weight descending (-0 counts as +0),
+// then the smaller slot. Keys of one row are distinct.
+__device__ __forceinline__ uint64_t sample_key(float w, uint32_t slot) {
+  uint32_t b = __float_as_uint(w + 0.f);
+  b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return (static_cast<uint64_t>(b) << 32) | (0xFFFFFFFFu - slot);
+}
+
+__device__ __forceinline__ uint32_t sample_key_slot(uint64_t key) {
+  return 0xFFFFFFFFu - static_cast<uint32_t>(key);
+}
+
+__global__ void sample_long_rows_kernel(const uint64_t* __restrict__ off,
+                                        uint32_t rows_n, uint32_t k,
+                                        uint32_t* __restrict__ flag) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < rows_n;
+       r += stride)
+    flag[r] = off[r + 1] - off[r] > k ? 1u : 0u;
+}
+
+__global__ void sample_topk_thread_kernel(
+    const uint64_t* __restrict__ off, const float* __restrict__ w,
+    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t k,
+    const uint64_t* __restrict__ rank, uint32_t* __restrict__ slots) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < nrows; i += stride) {
+    uint32_t r = rows[i];
+    const uint64_t b = off[r];
+    const uint32_t deg = static_cast<uint32_t>(off[r + 1] - b);
+    uint32_t* out = slots + rank[r] * k;
+    uint64_t prev = ~0ull;
+    for (uint32_t p = 0; p < k; ++p) {
+      uint64_t best = 0;
+      for (uint32_t j = 0; j < deg; ++j) {
+        uint64_t key = sample_key(w[b + j], j);
+        if (key < prev && key > best) best = key;
+      }
+      out[p] = sample_key_slot(best);
+      prev = best;
+    }
+  }
+}
+
+// a wave keeps the keys of its row (at most kSampleWaveDeg) in registers
+__global__ void sample_topk_wave_kernel(
+    const uint64_t* __restrict__ off, const float* __restrict__ w,
+    const uint32_t* __restrict__ rows, uint64_t nrows, uint32_t k,
+    const uint64_t* __restrict__ rank, uint32_t* __restrict__ slots) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t nwaves = (static_cast<uint64_t>(gridDim.x) * blockDim.x) >> 6;
+  for (uint64_t i = (static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                     threadIdx.x) >> 6;
+       i < nrows; i += nwaves) {
+    uint32_t r = rows[i];
+    const uint64_t b = off[r];
+    const uint32_t deg = static_cast<uint32_t>(off[r + 1] - b);
+    uint64_t key[kSampleWaveKeys];
+#pragma unroll
+    for (int j = 0; j < kSampleWaveKeys; ++j) {
+      uint32_t slot = j * kWave + lane;
+      key[j] = slot < deg ? sample_key(w[b + slot], slot) : 0;
+    }
+    uint32_t* out = slots + rank[r] * k;
+    uint64_t prev = ~0ull;
+    for (uint32_t p = 0; p < k; ++p) {
+      uint64_t best = 0;
+#pragma unroll
+      for (int j = 0; j < kSampleWaveKeys; ++j)
+        if (key[j] < prev && key[j] > best) best = key[j];
+      best = wave_max_u64(best);
+      if (lane == 0) out[p] = sample_key_slot(best);
+      prev = best;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBlock)
+sample_topk_block_kernel(const uint64_t* __restrict__ off,
+                         const float* __restrict__ w,
+                         const uint32_t* __restrict__ rows, uint64_t nrows,
+                         uint32_t k, const uint64_t* __restrict__ rank,
+                         uint32_t* __restrict__ slots) {
+  __shared__ uint64_t s_wave[kBlock / kWave];
+  const uint32_t lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  for (uint64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
+    uint32_t r = rows[i];
+    const uint64_t b = off[r];
+    const uint64_t deg = off[r + 1] - b;
+    uint32_t* out = slots + rank[r] * k;
+    uint64_t prev = ~0ull;
+    for (uint32_t p = 0; p < k; ++p) {
+      uint64_t best = 0;
+      for (uint64_t j = threadIdx.x; j < deg; j += kBlock) {
+        uint64_t key = sample_key(w[b + j], static_cast<uint32_t>(j));
+        if (key < prev && key > best) best = key;
+      }
+      best = wave_max_u64(best);
+      if (lane == 0) s_wave[wid] = best;
+      __syncthreads();
+#pragma unroll
+      for (uint32_t q = 0; q < kBlock / kWave; ++q)
+        if (s_wave[q] > best) best = s_wave[q];
+      if (threadIdx.x == 0) out[p] = sample_key_slot(best);
+      prev = best;
+      __syncthreads();
+    }
+  }
+}
+
+// --- walker queues ----------------------------------------------------------
+
+// cnt[0]: walkers in `next`, cnt[1]: steps taken, cnt[2 + p]: walkers in
+// peer p's send region (cap entries each)
+struct SampleQueues {
+  SampleWalker* next;
+  SampleWalker* peer;
+  unsigned long long* cnt;
+  uint64_t cap;
+  int rank;
+};
+
+// Wave-aggregated append of one walker per lane to the queue of its target
+// rank (target < 0: none): one atomic per wave and distinct target. Every
+// lane of the wave calls it.
+__device__ __forceinline__ void sample_append(const SampleQueues& q,
+                                              int target, SampleWalker wk) {
+  const uint32_t lane = threadIdx.x & 63;
+  unsigned long long remaining = __ballot(target >= 0);
+  while (remaining) {
+    const int L = __ffsll(remaining) - 1;
+    const int t0 = __shfl(target, L, 64);
+    const unsigned long long m = __ballot(target == t0) & remaining;
+    remaining &= ~m;
+    unsigned long long base = 0;
+    if (lane == static_cast<uint32_t>(L))
+      base = atomicAdd(t0 == q.rank ? q.cnt : q.cnt + 2 + t0,
+                       static_cast<unsigned long long>(__popcll(m)));
+    base = __shfl(base, L, 64);
+    if (target == t0) {
+      uint64_t at = base + __popcll(m & ((1ull << lane) - 1));
+      SampleWalker* dst =
+          t0 == q.rank ? q.next : q.peer + static_cast<uint64_t>(t0) * q.cap;
+      if (at < q.cap) dst[at] = wk;
+    }
+  }
+}
+
+// Walk i starts on starts[i] (through perm on a hub-renumbered graph); the
+// owner of that vertex writes paths[i][0] and queues the walker.
+__global__ void sample_seed_kernel(const uint32_t* __restrict__ starts,
+                                   uint64_t n_walks,
+                                   const uint32_t* __restrict__ perm,
+                                   uint32_t nv_global, uint32_t v_begin,
+                                   uint32_t v_end,
+                                   uint32_t* __restrict__ paths,
+                                   uint32_t row_len, bool more,
+                                   SampleQueues q) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                       (threadIdx.x - lane);
+       base < n_walks; base += stride) {
+    const uint64_t i = base + lane;
+    int target = -1;
+    SampleWalker wk{0, 0};
+    if (i < n_walks) {
+      uint32_t v = starts[i];
+      if (v < nv_global) {
+        if (perm) v = perm[v];
+        if (v >= v_begin && v < v_end) {
+          paths[i * row_len] = v;
+          if (more) {
+            target = q.rank;
+            wk = SampleWalker{v, static_cast<uint32_t>(i)};
+          }
+        }
+      }
+    }
+    sample_append(q, target, wk);
+  }
+}
+
+struct SampleIndex {
+  const float* __restrict__ cdf;          // edge_weight
+  const uint64_t* __restrict__ topk_rank;  // top_k on a weighted graph,
+  const uint32_t* __restrict__ topk_slots;  //   null otherwise
+  uint32_t k;
+};
+
+enum { kSampleRandom = 0, kSampleEdgeWeight = 1, kSampleTopK = 2 };
+
+// One lane per live walker of `cur`; `more`: hops remain after this one.
+template <int STRAT>
+__global__ void sample_step_kernel(DevGraphView g,
+                                   const SampleWalker* __restrict__ cur,
+                                   uint64_t n, SampleIndex ix,
+                                   uint32_t* __restrict__ paths,
+                                   uint32_t row_len, uint32_t hop, bool more,
+                                   uint64_t seed, SampleQueues q) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                       (threadIdx.x - lane);
+       base < n; base += stride) {
+    const uint64_t i = base + lane;
+    int target = -1;
+    SampleWalker out{0, 0};
+    bool stepped = false;
+    if (i < n) {
+      const SampleWalker wk = cur[i];
+      const bool here = g.is_owned(wk.v);  // always: the sender checked
+      const uint32_t row = here ? g.row(wk.v) : 0;
+      const uint64_t b = g.oe_off[row];
+      const uint64_t deg = here ? g.oe_off[row + 1] - b : 0;
+      if (deg) {
+        const uint64_t r = sample_draw(seed, wk.walk, hop);
+        uint64_t pick = deg;  // deg: dead end
+        if constexpr (STRAT == kSampleRandom) {
+          pick = __umul64hi(r, deg);
+        } else if constexpr (STRAT == kSampleEdgeWeight) {
+          const float* __restrict__ c = ix.cdf + b;
+          const float total = c[deg - 1];
+          if (total > 0.f) {
+            const float u =
+                static_cast<float>(static_cast<uint32_t>(r >> 40)) * 0x1p-24f;
+            const float t = __fmul_rn(u, total);
+            uint64_t lo = 0, hi = deg;
+            while (lo < hi) {
+              uint64_t mid = (lo + hi) >> 1;
+              if (c[mid] <= t)
+                lo = mid + 1;
+              else
+                hi = mid;
+            }
+            pick = lo < deg ? lo : deg - 1;
+          }
+        } else {
+          const uint64_t kk = deg < ix.k ? deg : ix.k;
+          pick = __umul64hi(r, kk);
+          if (ix.topk_slots && deg > ix.k)
+            pick = ix.topk_slots[ix.topk_rank[row] * ix.k + pick];
+        }
+        if (pick < deg) {
+          const uint32_t nv = g.oe_dst[b + pick];
+          paths[static_cast<uint64_t>(wk.walk) * row_len + hop + 1] = nv;
+          stepped = true;
+          if (more) {
+            target = g.owner(nv);
+            out = SampleWalker{nv, wk.walk};
+          }
+        }
+      }
+    }
+    const unsigned long long sm = __ballot(stepped);
+    if (lane == 0 && sm)
+      atomicAdd(q.cnt + 1, static_cast<unsigned long long>(__popcll(sm)));
+    sample_append(q, target, out);
+  }
+}
+
+// the rows of the owned walks out of the path table, hub renumbering undone
+__global__ void sample_gather_kernel(const uint32_t* __restrict__ paths,
+                                     const uint32_t* __restrict__ own,
+                                     uint64_t n_own, uint32_t row_len,
+                                     const uint32_t* __restrict__ inv,
+                                     uint32_t* __restrict__ out) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  const uint64_t total = n_own * row_len;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < total; i += stride) {
+    uint32_t x = paths[static_cast<uint64_t>(own[i / row_len]) * row_len +
+                       i % row_len];
+    if (inv && x != kSampleNoVertex) x = inv[x];
+    out[i] = x;
+  }
+}
+
+namespace {
+
+void ensure_sample_cdf(DeviceGraph& g, GpuContext::Impl& I, hipStream_t s) {
+  if (g.sample_cdf_built) return;
+  HIP_CHECK(hipStreamSynchronize(s));
+  const double t0 = wall_s();
+  const uint32_t owned = g.owned();
+  const uint64_t arcs = g.oe_dst.size();
+  g.sample_cdf.resize(arcs ? arcs : 1);
+  if (owned && arcs) {
+    DeviceBuffer<uint32_t> rt, rw, rb;
+    auto n = partition_rows(SampleLenTiers{g.oe_off.data(), 0}, owned,
+                            {&rt, &rw, &rb}, s);
+    const uint64_t* off = g.oe_off.data();
+    const float* w = g.oe_w.data();
+    float* cdf = g.sample_cdf.data();
+    if (n[2])
+      sample_cdf_block_kernel<<<std::min<uint64_t>(n[2], kMaxGrid), kBlock, 0,
+                                s>>>(off, w, rb.data(), n[2], cdf);
+    if (n[1])
+      sample_cdf_wave_kernel<<<grid_for(n[1] * kWave), kBlock, 0, s>>>(
+          off, w, rw.data(), n[1], cdf);
+    if (n[0])
+      sample_cdf_thread_kernel<<<grid_for(n[0]), kBlock, 0, s>>>(
+          off, w, rt.data(), n[0], cdf);
+    HIP_CHECK(hipStreamSynchronize(s));  // the row lists go out of scope
+  }
+  g.sample_cdf_built = true;
+  ++I.sample_dbg.cdf_builds;
+  I.sample_dbg.cdf_bytes = g.sample_cdf.size() * sizeof(float);
+  I.sample_dbg.cdf_ms = (wall_s() - t0) * 1e3;
+}
+
+void ensure_sample_topk(DeviceGraph& g, GpuContext::Impl& I, int k,
+                        hipStream_t s) {
+  if (g.sample_topk_k == k) return;
+  HIP_CHECK(hipStreamSynchronize(s));
+  const double t0 = wall_s();
+  const uint32_t owned = g.owned();
+  const uint32_t uk = static_cast<uint32_t>(k);
+  g.sample_topk_k = 0;
+  g.sample_topk_rank.resize(static_cast<size_t>(owned) + 1);
+  uint64_t n_long = 0;
+  {
+    DeviceBuffer<uint32_t> flag(owned ? owned : 1);
+    if (owned)
+      sample_long_rows_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+          g.oe_off.data(), owned, uk, flag.data());
+    n_long = exclusive_scan(flag.data(), g.sample_topk_rank.data(), owned, s,
+                            I.scan);
+  }
+  g.sample_topk_slots.resize(n_long ? n_long * uk : 1);
+  if (n_long) {
+    DeviceBuffer<uint32_t> rt, rw, rb;
+    auto n = partition_rows(SampleLenTiers{g.oe_off.data(), uk}, owned,
+                            {&rt, &rw, &rb}, s);
+    const uint64_t* off = g.oe_off.data();
+    const float* w = g.oe_w.data();
+    const uint64_t* rank = g.sample_topk_rank.data();
+    uint32_t* slots = g.sample_topk_slots.data();
+    if (n[2])
+      sample_topk_block_kernel<<<std::min<uint64_t>(n[2], kMaxGrid), kBlock,
+                                 0, s>>>(off, w, rb.data(), n[2], uk, rank,
+                                         slots);
+    if (n[1])
+      sample_topk_wave_kernel<<<grid_for(n[1] * kWave), kBlock, 0, s>>>(
+          off, w, rw.data(), n[1], uk, rank, slots);
+    if (n[0])
+      sample_topk_thread_kernel<<<grid_for(n[0]), kBlock, 0, s>>>(
+          off, w, rt.data(), n[0], uk, rank, slots);
+    HIP_CHECK(hipStreamSynchronize(s));  // the row lists go out of scope
+  }
+  g.sample_topk_k = k;
+  ++I.sample_dbg.topk_builds;
+  I.sample_dbg.topk_bytes = g.sample_topk_rank.size() * sizeof(uint64_t) +
+                            g.sample_topk_slots.size() * sizeof(uint32_t);
+  I.sample_dbg.topk_ms = (wall_s() - t0) * 1e3;
+}
+
+template <int STRAT>
+void launch_sample_step(hipStream_t s, const DevGraphView& view,
+                        const SampleWalker* cur, uint64_t n,
+                        const SampleIndex& ix, uint32_t* paths,
+                        uint32_t row_len, uint32_t hop, bool more,
+                        uint64_t seed, const SampleQueues& q) {
+  sample_step_kernel<STRAT><<<grid_for(n), kBlock, 0, s>>>(
+      view, cur, n, ix, paths, row_len, hop, more, seed, q);
+}
+
+}  // namespace
+
+GpuRunResult GpuContext::sample(DeviceGraph& g,
+                                const std::vector<uint32_t>& starts,
+                                int hops, int strategy, int top_k,
+                                uint64_t seed) {
+  RangeMarker _mk("grapehip::sample");
+  auto& I = *impl_;
+  hipStream_t s = I.compute;
+  if (strategy < kSampleRandom || strategy > kSampleTopK)
+    throw std::runtime_error("sample: strategy must be 0, 1 or 2");
+  if (hops < 0) throw std::runtime_error("sample: hops must be >= 0");
+  if (strategy == kSampleTopK && (top_k < 1 || top_k > kSampleTopKMax))
+    throw std::runtime_error("sample: top_k = " + std::to_string(top_k) +
+                             " is outside 1.." +
+                             std::to_string(kSampleTopKMax) +
+                             " (kSampleTopKMax) of the device sampler");
+  const uint64_t n_walks = starts.size();
+  const uint32_t row_len = static_cast<uint32_t>(hops) + 1;
+  if (n_walks >= 0xFFFFFFFFull)
+    throw std::runtime_error("sample: the walk index must fit in 32 bits");
+  const bool multi = world_ > 1;
+  // every weight of an unweighted graph is 1
+  if (strategy == kSampleEdgeWeight && !g.weighted) strategy = kSampleRandom;
+  SampleIndex ix{nullptr, nullptr, nullptr, static_cast<uint32_t>(top_k)};
+  if (strategy == kSampleEdgeWeight) {
+    ensure_sample_cdf(g, I, s);
+    ix.cdf = g.sample_cdf.data();
+  } else if (strategy == kSampleTopK && g.weighted) {
+    ensure_sample_topk(g, I, top_k, s);
+    ix.topk_rank = g.sample_topk_rank.data();
+    ix.topk_slots = g.sample_topk_slots.data();
+  }
+
+  // the walks that start here, by the ids as loaded: the hub renumbering
+  // permutes inside a slice, so it keeps the owner
+  std::vector<uint32_t> own;
+  for (uint64_t i = 0; i < n_walks; ++i)
+    if (starts[i] < g.nv_global && starts[i] >= g.v_begin &&
+        starts[i] < g.v_end)
+      own.push_back(static_cast<uint32_t>(i));
+
+  const uint64_t cap = n_walks ? n_walks : 1;
+  grow(I.sample_q[0], cap);
+  grow(I.sample_q[1], cap);
+  if (multi) grow(I.sample_peer, cap * world_);
+  grow(I.sample_cnt, static_cast<size_t>(world_) + 2);
+  grow(I.sample_paths, cap * row_len);
+  grow(I.sample_starts, cap);
+  grow(I.sample_own, own.size() ? own.size() : 1);
+  grow(I.sample_out, own.size() ? own.size() * row_len : 1);
+  const size_t n_cnt = static_cast<size_t>(world_) + 2;
+  DevGraphView view = make_view(g, rank_, world_);
+
+  RunBracket br(I, comm_);
+
+  if (n_walks)
+    HIP_CHECK(hipMemcpyAsync(I.sample_starts.data(), starts.data(),
+                             n_walks * 4, hipMemcpyHostToDevice, s));
+  fill(I.sample_paths.data(), kSampleNoVertex, n_walks * row_len, s);
+  HIP_CHECK(hipMemsetAsync(I.sample_cnt.data(), 0, n_cnt * 8, s));
+  int cur = 0;
+  auto queues = [&](int next) {
+    return SampleQueues{
+        reinterpret_cast<SampleWalker*>(I.sample_q[next].data()),
+        reinterpret_cast<SampleWalker*>(I.sample_peer.data()),
+        I.sample_cnt.data(), cap, rank_};
+  };
+  if (n_walks)
+    sample_seed_kernel<<<grid_for(n_walks), kBlock, 0, s>>>(
+        I.sample_starts.data(), n_walks,
+        g.permuted ? g.perm.data() : nullptr, g.nv_global, g.v_begin,
+        g.v_end, I.sample_paths.data(), row_len, hops > 0, queues(cur));
+  std::vector<unsigned long long> c(n_cnt);
+  HIP_CHECK(hipMemcpyAsync(c.data(), I.sample_cnt.data(), n_cnt * 8,
+                           hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  uint64_t n_cur = c[0];
+  uint64_t live = multi ? comm_->allreduce_sum(n_cur) : n_cur;
+  uint64_t steps = 0;
+  int rounds = 0;
+  for (int hop = 0; hop < hops && live; ++hop) {
+    ++rounds;
+    const bool more = hop + 1 < hops;
+    const int nxt = cur ^ 1;
+    HIP_CHECK(hipMemsetAsync(I.sample_cnt.data(), 0, n_cnt * 8, s));
+    if (n_cur) {
+      auto launch = strategy == kSampleRandom
+                        ? launch_sample_step<kSampleRandom>
+                        : (strategy == kSampleEdgeWeight
+                               ? launch_sample_step<kSampleEdgeWeight>
+                               : launch_sample_step<kSampleTopK>);
+      launch(s, view,
+             reinterpret_cast<const SampleWalker*>(I.sample_q[cur].data()),
+             n_cur, ix, I.sample_paths.data(), row_len,
+             static_cast<uint32_t>(hop), more, seed, queues(nxt));
+    }
+    // the one count read per round
+    HIP_CHECK(hipMemcpyAsync(c.data(), I.sample_cnt.data(), n_cnt * 8,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    steps += c[1];
+    uint64_t n_next = c[0];
+    live = n_next;
+    if (multi && more) {
+      // lengths on the control plane: [p] walkers for peer p, [world] the
+      // walkers that stay
+      std::vector<uint64_t> mine(world_ + 1), all(
+          static_cast<size_t>(world_) * (world_ + 1));
+      for (int p = 0; p < world_; ++p) mine[p] = p == rank_ ? 0 : c[2 + p];
+      mine[world_] = n_next;
+      comm_->allgather(mine.data(), mine.size() * 8, all.data());
+      std::vector<uint64_t> send_off(world_ + 1, 0), recv_off(world_ + 1, 0);
+      live = 0;
+      for (int p = 0; p < world_; ++p) {
+        const uint64_t* row = all.data() + static_cast<size_t>(p) *
+                                               (world_ + 1);
+        send_off[p + 1] = send_off[p] + mine[p] * sizeof(SampleWalker);
+        recv_off[p + 1] = recv_off[p] + row[rank_] * sizeof(SampleWalker);
+        for (int t = 0; t <= world_; ++t) live += row[t];
+      }
+      const uint64_t n_recv = recv_off[world_] / sizeof(SampleWalker);
+      if (n_next + n_recv > cap)
+        throw std::runtime_error("sample: more walkers than walks");
+      // regions packed in peer order; the payload lands behind the walkers
+      // that stayed
+      if (I.sendbuf.size() < send_off[world_])
+        I.sendbuf.resize(send_off[world_] + (1 << 20));
+      for (int p = 0; p < world_; ++p)
+        if (mine[p])
+          HIP_CHECK(hipMemcpyAsync(
+              I.sendbuf.data() + send_off[p],
+              I.sample_peer.data() + static_cast<uint64_t>(p) * cap,
+              mine[p] * sizeof(SampleWalker), hipMemcpyDeviceToDevice, s));
+      I.dc.sendrecv(I.sendbuf.data(), send_off,
+                    reinterpret_cast<uint8_t*>(I.sample_q[nxt].data() +
+                                               n_next),
+                    recv_off, s);
+      n_next += n_recv;
+    }
+    n_cur = n_next;
+    cur = nxt;
+  }
+  // each slot was written by at most one rank over 0xFFFFFFFF
+  if (multi && n_walks)
+    I.dc.allreduce_min_u32(I.sample_paths.data(), n_walks * row_len, s);
+  std::vector<uint32_t> paths_h;
+  if (!own.empty()) {
+    HIP_CHECK(hipMemcpyAsync(I.sample_own.data(), own.data(), own.size() * 4,
+                             hipMemcpyHostToDevice, s));
+    sample_gather_kernel<<<grid_for(own.size() * row_len), kBlock, 0, s>>>(
+        I.sample_paths.data(), I.sample_own.data(), own.size(), row_len,
+        g.permuted ? g.inv.data() : nullptr, I.sample_out.data());
+    paths_h.resize(own.size() * row_len);
+    HIP_CHECK(hipMemcpyAsync(paths_h.data(), I.sample_out.data(),
+                             paths_h.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  if (multi) steps = comm_->allreduce_sum(steps);
+  ++I.sample_dbg.calls;
+  I.sample_dbg.steps = steps;
+  GpuRunResult res = br.finish(rounds, steps);
+  res.paths = std::move(paths_h);
+  res.walk_ids.assign(own.begin(), own.end());
+  return res;
+}
+
+GpuContext::SampleDebug GpuContext::debug_sample(bool reset) {
+  SampleDebug out = impl_->sample_dbg;
+  if (reset)
+    impl_->sample_dbg.calls = impl_->sample_dbg.cdf_builds =
+        impl_->sample_dbg.topk_builds = impl_->sample_dbg.steps = 0;
   return out;
 }
 

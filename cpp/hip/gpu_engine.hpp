@@ -115,6 +115,18 @@ struct DeviceGraph {
   // pr_dangling: [0]=current dangling sum, [1]=next, [2]=previous base
   DeviceBuffer<double> pr_rank, pr_acc, pr_dangling;
   DeviceBuffer<float> pr_contrib;
+  // random-walk sampler indexes (built lazily by sample(), kept with the
+  // graph). sample_cdf: inclusive fp32 prefix sum of the weights inside each
+  // stored out-row, 4 B per stored arc (edge_weight on weighted graphs).
+  // Top-k index for one k at a time (top_k on weighted graphs), only for
+  // rows longer than k: sample_topk_rank[r] = how many such rows precede
+  // row r (8 B per owned row), sample_topk_slots[rank * k + j] = row slot of
+  // the j-th heaviest arc, ties to the smaller slot (4 * k B per such row).
+  DeviceBuffer<float> sample_cdf;
+  bool sample_cdf_built = false;
+  DeviceBuffer<uint64_t> sample_topk_rank;
+  DeviceBuffer<uint32_t> sample_topk_slots;
+  int sample_topk_k = 0;  // 0: no index yet
   ~DeviceGraph();
 };
 
@@ -129,10 +141,21 @@ struct GpuRunResult {
   // p2p halo/mirror/row-fetch vs collective traffic)
   uint64_t bytes_p2p = 0, bytes_coll = 0;
   uint64_t count = 0;  // kclique: the global number of k-cliques
+  // sample: indices into `starts` of the walks that begin on an owned
+  // vertex, ascending, and their paths, [walk_ids.size()][hops + 1] device
+  // ids of the graph as it was loaded (hub renumbering undone), 0xFFFFFFFF
+  // from the first dead end on
+  std::vector<int64_t> walk_ids;
+  std::vector<uint32_t> paths;
 };
 
 // largest k of the device kclique (its mask stack is k - 2 registers deep)
 constexpr int kCliqueMaxK = 8;
+// largest top_k of the device sampler (the index is built by top_k arg-max
+// passes over a row)
+constexpr int kSampleTopKMax = 32;
+// a start of sample() that is no vertex of the graph
+constexpr uint32_t kSampleNoVertex = 0xFFFFFFFFu;
 
 class GpuContext {
  public:
@@ -173,6 +196,14 @@ class GpuContext {
   // enumeration over the degree-oriented CSR; count: the global total on
   // every rank
   GpuRunResult kclique(DeviceGraph& g, int k);
+  // random walks of `hops` steps on the stored out-CSR, one per entry of
+  // `starts` (device ids of the graph as loaded, kSampleNoVertex for a start
+  // that is no vertex; every rank passes the same list). strategy: 0 random,
+  // 1 edge_weight, 2 top_k (cpp/apps/sampler.hpp SampleStrategy). The draw
+  // of a step depends on (seed, index into starts, hop) alone. rounds: hops
+  // that still had a live walk; traversed_edges: steps taken, global.
+  GpuRunResult sample(DeviceGraph& g, const std::vector<uint32_t>& starts,
+                      int hops, int strategy, int top_k, uint64_t seed);
 
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device
@@ -195,6 +226,15 @@ class GpuContext {
   // the wave, block and global tiers, kCliqueBlockMax and kCliqueMaxK, in
   // that order. reset zeroes the first four after the read.
   std::array<uint64_t, 6> debug_kclique(bool reset = false);
+  // test hook: device sample() calls, cdf and top-k index builds so far,
+  // the steps of the last call, and the bytes and build time of the last
+  // index built of each kind. reset zeroes the counts after the read.
+  struct SampleDebug {
+    uint64_t calls = 0, cdf_builds = 0, topk_builds = 0, steps = 0;
+    uint64_t cdf_bytes = 0, topk_bytes = 0;
+    double cdf_ms = 0, topk_ms = 0;
+  };
+  SampleDebug debug_sample(bool reset = false);
   // test hook: the id-segment layout of g, built if it is not yet (empty
   // rows when the path is off for g), with the pull CSR it was cut from
   struct PrSegDebug {

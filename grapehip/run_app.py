@@ -24,7 +24,7 @@ import grapehip
 from grapehip.io import read_ldbc_edges, read_ldbc_vertices
 
 APPS = ("bfs", "sssp", "pagerank", "wcc", "cdlp", "lcc", "bc", "kcore",
-        "core_decomposition", "kclique")
+        "core_decomposition", "kclique", "sample")
 
 
 def build_parser():
@@ -51,6 +51,13 @@ def build_parser():
     ap.add_argument("--cdlp_mr", type=int, default=10)
     ap.add_argument("--kcore_k", type=int, default=3)
     ap.add_argument("--kclique_k", type=int, default=3)
+    # random walks from the vertices 0..N-1 (reference gnn_sampler)
+    ap.add_argument("--sample_walks", type=int, default=16)
+    ap.add_argument("--sample_hops", type=int, default=2)
+    ap.add_argument("--sample_strategy", default="random",
+                    choices=("random", "edge_weight", "top_k"))
+    ap.add_argument("--sample_top_k", type=int, default=4)
+    ap.add_argument("--sample_seed", type=int, default=7)
     # delta mutation (LoadGraphAndMutate, loader.h:55-68 +
     # ev_fragment_mutator.h: base graph + additions/removals files)
     ap.add_argument("--efile_add", default="")
@@ -162,6 +169,13 @@ def main(argv=None):
         res = eng.core_decomposition(g)
     elif app == "kclique":
         res = eng.kclique(g, args.kclique_k)
+    elif app == "sample":
+        # --gpu walks on the device; without it the host app runs
+        res = eng.sample(g, np.arange(args.sample_walks, dtype=np.int64),
+                         hops=args.sample_hops,
+                         strategy=args.sample_strategy,
+                         top_k=args.sample_top_k, seed=args.sample_seed,
+                         device=args.gpu)
     timers.append(("run algorithm", time.time() - t))
 
     t = time.time()
@@ -173,6 +187,10 @@ def main(argv=None):
             if app == "kclique":
                 if rank == 0:
                     f.write("%d\n" % res["clique_count"])
+            elif app == "sample":
+                # one line per owned walk: walk_id v0 v1 ...
+                for wid, path in zip(res["walk_ids"], res["paths"]):
+                    f.write("%d %s\n" % (wid, " ".join(map(str, path))))
             else:
                 for oid, val in zip(res["oids"], res["values"]):
                     f.write("%d %s\n" % (oid, fmt_value(val)))

@@ -384,6 +384,16 @@ PYBIND11_MODULE(_core, m) {
 #endif
            },
            py::arg("reset") = false)
+      .def("_debug_arc_depth",
+           [](PyEngine& e) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (!e.gpu) throw std::runtime_error("no gpu engine");
+             return e.gpu->debug_arc_depth();
+#else
+             throw std::runtime_error("no hip");
+             return 0;
+#endif
+           })
       .def("_debug_kclique",
            [](PyEngine& e, bool reset) {
 #ifdef GRAPEHIP_WITH_HIP

@@ -2147,11 +2147,43 @@ __device__ __forceinline__ uint32_t xcc_id() {
   return __builtin_amdgcn_s_getreg(((4 - 1) << 11) | kHwRegXccId);
 }
 
+// One window of 64 consecutive arcs of a wave's quarter: sums each span's run
+// in lane order, continues the run carried in from the window before, stores
+// a run that ends inside the window to wacc[owner] and carries the last one.
+__device__ __forceinline__ void pr_seg_scan_window(int lane, bool act,
+                                                   int owner, double c,
+                                                   double* wacc, double& carry,
+                                                   int& carry_owner) {
+  const int oprev = __shfl_up(owner, 1, 64);
+  const bool head = (lane == 0) || oprev != owner;
+  const unsigned long long hb = __ballot(head);
+  const unsigned long long mine =
+      hb & ((lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1));
+  const int seg = 63 - __clzll(mine);
+  double sum = c;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    double up = __shfl_up(sum, d, 64);
+    if (lane - d >= seg) sum += up;
+  }
+  // the run that opens the window continues the carried one, or the
+  // carried one is complete
+  if (carry_owner >= 0) {
+    if (owner == carry_owner && seg == 0) sum = carry + sum;
+    const int o0 = __shfl(owner, 0, 64);
+    if (o0 != carry_owner && lane == 0) wacc[carry_owner] = carry;
+  }
+  const bool tail = (lane == 63) || ((hb >> (lane + 1)) & 1ull);
+  if (tail && act && lane != 63) wacc[owner] = sum;
+  carry = __shfl(sum, 63, 64);
+  carry_owner = __shfl(owner, 63, 64);
+}
+
 constexpr int kPrSegBlocksPerCu = 8;
 
 // Persistent: CUs x kPrSegBlocksPerCu workgroups, each taking items from
 // per-segment counters (ctr, zeroed before every launch).
-template <bool NT>
+template <bool NT, int DEPTH>
 __global__ void __launch_bounds__(kBlock)
 pr_pull_seg_kernel(PrSegView v, const uint32_t* __restrict__ dst,
                    const float* __restrict__ contrib,
@@ -2237,43 +2269,62 @@ pr_pull_seg_kernel(PrSegView v, const uint32_t* __restrict__ dst,
         }
         double carry = 0.0;
         int carry_owner = -1;
-        for (uint64_t w0 = ws; w0 < we; w0 += kWave) {
-          const uint64_t e = w0 + lane;
-          const bool act = e < we;
-          int owner = -1;
-          double c = 0.0;
-          if (act) {
-            while (lo + 1 < n && s_off[lo + 1] <= e) ++lo;
-            owner = lo;
-            const uint64_t idx = s_base[lo] + (e - s_off[lo]);
-            const uint32_t d = NT ? __builtin_nontemporal_load(dst + idx)
-                                  : dst[idx];
-            c = static_cast<double>(contrib[d]);
-          }
-          const int oprev = __shfl_up(owner, 1, 64);
-          const bool head = (lane == 0) || oprev != owner;
-          const unsigned long long hb = __ballot(head);
-          const unsigned long long mine =
-              hb & ((lane == 63) ? ~0ull : ((1ull << (lane + 1)) - 1));
-          const int seg = 63 - __clzll(mine);
-          double sum = c;
+        for (uint64_t g0 = ws; g0 < we; g0 += DEPTH * kWave) {
+          // a group of DEPTH windows: every dst load, then every gather,
+          // then the scans in window order (KERNELS.md "Arc depth")
+          bool act[DEPTH];
+          int owner[DEPTH];
+          float cf[DEPTH];
+          if constexpr (DEPTH == 1) {
+            const uint64_t e = g0 + lane;
+            act[0] = e < we;
+            owner[0] = -1;
+            cf[0] = 0.0f;
+            if (act[0]) {
+              while (lo + 1 < n && s_off[lo + 1] <= e) ++lo;
+              owner[0] = lo;
+              const uint64_t idx = s_base[lo] + (e - s_off[lo]);
+              const uint32_t d = NT ? __builtin_nontemporal_load(dst + idx)
+                                    : dst[idx];
+              cf[0] = contrib[d];
+            }
+          } else {
+            // a lane past the quarter's end loads arc 0 of the CSR, which
+            // exists (the segment has an item), and drops the value: the
+            // loads stay unconditional, so none waits for another
+            uint64_t idx[DEPTH];
+            uint32_t d[DEPTH];
 #pragma unroll
-          for (int d = 1; d < 64; d <<= 1) {
-            double up = __shfl_up(sum, d, 64);
-            if (lane - d >= seg) sum += up;
+            for (int j = 0; j < DEPTH; ++j) {
+              const uint64_t e = g0 + j * kWave + lane;
+              act[j] = e < we;
+              owner[j] = -1;
+              idx[j] = 0;
+              if (act[j]) {
+                while (lo + 1 < n && s_off[lo + 1] <= e) ++lo;
+                owner[j] = lo;
+                idx[j] = s_base[lo] + (e - s_off[lo]);
+              }
+            }
+#pragma unroll
+            for (int j = 0; j < DEPTH; ++j)
+              d[j] = NT ? __builtin_nontemporal_load(dst + idx[j])
+                        : dst[idx[j]];
+            // left alone, the scheduler interleaves the rounds again to
+            // save registers (load, wait, load, wait): fence them
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int j = 0; j < DEPTH; ++j) cf[j] = contrib[d[j]];
+            __builtin_amdgcn_sched_barrier(0);
           }
-          // the run that opens the window continues the carried one, or the
-          // carried one is complete
-          if (carry_owner >= 0) {
-            if (owner == carry_owner && seg == 0) sum = carry + sum;
-            const int o0 = __shfl(owner, 0, 64);
-            if (o0 != carry_owner && lane == 0)
-              s_wacc[wid][carry_owner] = carry;
+#pragma unroll
+          for (int j = 0; j < DEPTH; ++j) {
+            // the quarter may end inside the group (the same for all lanes)
+            if (DEPTH > 1 && g0 + j * kWave >= we) break;
+            const double c = act[j] ? static_cast<double>(cf[j]) : 0.0;
+            pr_seg_scan_window(lane, act[j], owner[j], c, s_wacc[wid], carry,
+                               carry_owner);
           }
-          const bool tail = (lane == 63) || ((hb >> (lane + 1)) & 1ull);
-          if (tail && act && lane != 63) s_wacc[wid][owner] = sum;
-          carry = __shfl(sum, 63, 64);
-          carry_owner = __shfl(owner, 63, 64);
         }
         if (carry_owner >= 0 && lane == 0) s_wacc[wid][carry_owner] = carry;
         __syncthreads();
@@ -2987,6 +3038,27 @@ std::array<uint64_t, 4> GpuContext::debug_expand_counts(bool reset) {
   }
   return out;
 }
+
+// GRAPEHIP_ARC_DEPTH: the 64-arc windows whose gathers a wave of
+// pr_pull_seg_kernel keeps in flight, read once per process. 1, 2 and 4 are
+// built; anything else is the default. The small pull and the frontier
+// expansion stay at one arc per lane: batched the same way they were slower
+// or gained less than the benchmark can show (profiles/r12_arc_depth.md).
+constexpr int kArcDepthDefault = 4;
+
+static int arc_depth() {
+  static const int depth = [] {
+    const char* e = getenv("GRAPEHIP_ARC_DEPTH");
+    if (!e || !*e) return kArcDepthDefault;
+    char* end = nullptr;
+    const long v = strtol(e, &end, 10);
+    return *end == '\0' && (v == 1 || v == 2 || v == 4) ? static_cast<int>(v)
+                                                        : kArcDepthDefault;
+  }();
+  return depth;
+}
+
+int GpuContext::debug_arc_depth() { return arc_depth(); }
 
 std::array<uint64_t, 2> GpuContext::debug_pr_path(bool reset) {
   std::array<uint64_t, 2> out = {impl_->pr_path_counts[0],
@@ -4591,14 +4663,22 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
         // reduce; the kernel boundary carries them across the XCDs.
         g.seg_ctr.zero(s);
         const int grid = I.num_cus * kPrSegBlocksPerCu;
-        if (pr_seg_knobs().nt)
-          pr_pull_seg_kernel<true><<<grid, kBlock, 0, s>>>(
-              g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
-              g.seg_part.data());
-        else
-          pr_pull_seg_kernel<false><<<grid, kBlock, 0, s>>>(
-              g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
-              g.seg_part.data());
+        auto pull_seg = [&](auto depth) {
+          constexpr int D = decltype(depth)::value;
+          if (pr_seg_knobs().nt)
+            pr_pull_seg_kernel<true, D><<<grid, kBlock, 0, s>>>(
+                g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
+                g.seg_part.data());
+          else
+            pr_pull_seg_kernel<false, D><<<grid, kBlock, 0, s>>>(
+                g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
+                g.seg_part.data());
+        };
+        switch (arc_depth()) {
+          case 4: pull_seg(std::integral_constant<int, 4>{}); break;
+          case 2: pull_seg(std::integral_constant<int, 2>{}); break;
+          default: pull_seg(std::integral_constant<int, 1>{});
+        }
         pr_seg_reduce_kernel<<<grid_for(g.n_seg_rows), kBlock, 0, s>>>(
             g.seg_rows.data(), g.seg_row_first.data(), g.n_seg_rows,
             g.seg_part.data(), g.v_begin, acc.data());

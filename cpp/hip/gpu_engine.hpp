@@ -222,6 +222,9 @@ class GpuContext {
   // the id-segment pull [0] or the row-tier pulls [1] (single-GPU row pull
   // only; the tiled and multi-GPU paths count as neither)
   std::array<uint64_t, 2> debug_pr_path(bool reset = false);
+  // test hook: the arc depth in effect (GRAPEHIP_ARC_DEPTH, read once per
+  // process; KERNELS.md "Arc depth")
+  int debug_arc_depth();
   // test hook: device kclique() calls so far, the rows of the last call in
   // the wave, block and global tiers, kCliqueBlockMax and kCliqueMaxK, in
   // that order. reset zeroes the first four after the read.

@@ -467,6 +467,40 @@ PYBIND11_MODULE(_core, m) {
              return py::dict();
 #endif
            })
+      .def("_debug_csr",
+           [](PyEngine& e, PyGraph& g) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (!e.gpu) throw std::runtime_error("no gpu engine");
+             if (!g.dev) throw std::runtime_error("not a device graph");
+             auto as_array = [](const auto& v) {
+               return py::array_t<typename std::decay_t<decltype(v)>::
+                                      value_type>(v.size(), v.data());
+             };
+             auto c = e.gpu->debug_csr(*g.dev);
+             py::dict d;
+             d["v_begin"] = c.v_begin;
+             d["off"] = as_array(c.off);
+             d["dst"] = as_array(c.dst);
+             d["w"] = c.weighted ? py::object(as_array(c.w)) : py::none();
+             d["in_off"] =
+                 c.has_in ? py::object(as_array(c.in_off)) : py::none();
+             d["in_dst"] =
+                 c.has_in ? py::object(as_array(c.in_dst)) : py::none();
+             d["in_w"] = c.has_in && c.weighted
+                             ? py::object(as_array(c.in_w))
+                             : py::none();
+             d["old_of_new"] =
+                 c.permuted ? py::object(as_array(c.old_of_new)) : py::none();
+             d["new_of_old"] =
+                 c.permuted ? py::object(as_array(c.new_of_old)) : py::none();
+             return d;
+#else
+             (void)e;
+             (void)g;
+             throw std::runtime_error("no hip");
+             return py::dict();
+#endif
+           })
       .def("_debug_scan",
            [](PyEngine& e, std::vector<uint32_t> in) {
 #ifdef GRAPEHIP_WITH_HIP

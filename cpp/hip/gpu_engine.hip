@@ -3754,6 +3754,34 @@ GpuContext::PrSegDebug GpuContext::debug_pr_segments(DeviceGraph& g) {
   return d;
 }
 
+GpuContext::CsrDebug GpuContext::debug_csr(const DeviceGraph& g) {
+  if (world_ > 1)
+    throw std::runtime_error("debug_csr: single-GPU graphs only");
+  hipStream_t s = impl_->compute;
+  // an empty buffer has no device pointer to copy from
+  auto get = [s](const auto& b) {
+    return b.size() ? b.download(s) : decltype(b.download(s)){};
+  };
+  CsrDebug d;
+  d.v_begin = g.v_begin;
+  d.weighted = g.weighted;
+  d.has_in = g.has_in;
+  d.permuted = g.permuted;
+  d.off = get(g.oe_off);
+  d.dst = get(g.oe_dst);
+  if (g.weighted) d.w = get(g.oe_w);
+  if (g.has_in) {
+    d.in_off = get(g.ie_off);
+    d.in_dst = get(g.ie_dst);
+    if (g.weighted) d.in_w = get(g.ie_w);
+  }
+  if (g.permuted) {
+    d.old_of_new = get(g.inv);
+    d.new_of_old = get(g.perm);
+  }
+  return d;
+}
+
 static void ensure_pr_tiles(DeviceGraph& g, GpuContext::Impl& I,
                             hipStream_t s) {
   if (g.pr_tiles_built) return;

@@ -251,6 +251,18 @@ class GpuContext {
     uint64_t bytes = 0;
   };
   PrSegDebug debug_pr_segments(DeviceGraph& g);
+  // test hook: the stored graph of g as it lies on the device, in stored
+  // ids: row r of off/in_off is vertex v_begin + r. The in arrays are empty
+  // without an in-CSR, w/in_w on an unweighted graph, old_of_new/new_of_old
+  // (inv/perm) on a graph that is not hub-renumbered. Copies only; world 1.
+  struct CsrDebug {
+    uint32_t v_begin = 0;
+    bool weighted = false, has_in = false, permuted = false;
+    std::vector<uint64_t> off, in_off;
+    std::vector<uint32_t> dst, in_dst, old_of_new, new_of_old;
+    std::vector<float> w, in_w;
+  };
+  CsrDebug debug_csr(const DeviceGraph& g);
   int device_id() const { return dev_; }
   TcpComm* comm() { return comm_; }
   int rank() const { return rank_; }

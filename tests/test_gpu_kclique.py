@@ -212,9 +212,11 @@ def test_limits_raise(eng, synthetic):
 
 
 def test_gpu_equals_host_rmat(eng):
-    """The synthetic generator keeps its edges on the device, so the host
-    comparison runs on RMAT edges of the same size loaded into both engines
-    (as test_gpu_kcore does): 2^15 x 5 arcs folded into 20,000 vertices."""
+    """GPU against the host app on RMAT edges of the size of the synthetic
+    graph, loaded into both engines (as test_gpu_kcore does): 2^15 x 5 arcs
+    folded into 20,000 vertices. The synthetic graph itself is counted
+    against kclique_oracle in tests/test_gpu_synthetic_oracle.py, which
+    models the generator's edges on the host."""
     src, dst, _, _ = grapehip.rmat_edges(15, edge_factor=5, seed=97)
     src, dst = src[:160000] % 20000, dst[:160000] % 20000
     cpu = grapehip.Engine(rank=0, world=1, master_port=29732)

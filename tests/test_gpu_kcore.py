@@ -182,6 +182,8 @@ def test_device_only_graph_result_dict(eng, synthetic):
 def test_gpu_equals_host_rmat(eng):
     # rmat_edges sizes are powers of two: draw 2^15 x 5 = 163,840 arcs,
     # fold the ids into 20,000 vertices and keep the first 160,000
+    # (the synthetic graph itself is held to the oracles in
+    # tests/test_gpu_synthetic_oracle.py, which models the generator's edges)
     src, dst, _, _ = grapehip.rmat_edges(15, edge_factor=5, seed=97)
     src, dst = src[:160000] % 20000, dst[:160000] % 20000
     cpu = grapehip.Engine(rank=0, world=1, master_port=29722)

@@ -7,15 +7,20 @@
 // messages, and every sampled step is reported back to the walk's origin
 // fragment the same way. Kafka streaming in/out (kafka_consumer.h) is not
 // available in this environment; the Python driver replays edge streams
-// through mutate_graph instead.
+// through mutate_graph instead. FanoutSamplerApp below is the reference's
+// --hop_and_num query (fan-out neighbourhood sampling) over the same engine.
 #pragma once
 
 #include <algorithm>
 #include <cstdint>
 #include <mutex>
 #include <random>
+#include <stdexcept>
+#include <string>
+#include <utility>
 #include <vector>
 
+#include "../core/fanout.hpp"
 #include "../core/fragment.hpp"
 #include "../core/message_manager.hpp"
 
@@ -253,6 +258,233 @@ class SamplerApp {
 
  private:
   std::vector<SamplerContext::Live> next_live_;
+};
+
+// ---------------------------------------------------------------------------
+// Fan-out (neighbourhood) sampling, CPU path. Reference parity:
+// examples/gnn_sampler --hop_and_num f_1-...-f_H (sampler.h hop_size /
+// next_pos): f_1 neighbours of every seed, f_2 of each of those, ..., with
+// replacement, one flat row of 1 + S ids per seed (core/fanout.hpp).
+//
+// The draws are those of the device path (hip/gpu_engine.hip sample_draw and
+// sample_pick), so host, device and the NumPy oracle agree entry for entry:
+// the draw of sample slot pos of seed index i is draw(seed, i, pos), taken
+// out of the parent's out-row in stored order, which is ascending gid (the
+// device's ascending device id).
+// ---------------------------------------------------------------------------
+
+inline uint64_t fanout_draw(uint64_t seed, uint64_t walk, uint64_t hop) {
+  uint64_t x = seed * 0x9E3779B97F4A7C15ULL + walk * 0xD1B54A32D192ED03ULL +
+               hop;
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ULL;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBULL;
+  return x ^ (x >> 31);
+}
+
+inline uint64_t fanout_mulhi(uint64_t a, uint64_t b) {
+  return static_cast<uint64_t>(
+      (static_cast<unsigned __int128>(a) * b) >> 64);
+}
+
+struct FanoutContext {
+  SampleStrategy strategy = SampleStrategy::kRandom;
+  int top_k = 4;
+  uint64_t seed = 7;
+  FanoutLayout lay;
+  int level = 0;  // the level the live nodes sit on
+  // the out-rows of the inner vertices in stored order (ascending gid,
+  // parallel arcs in fragment order); cdf: inclusive fp32 prefix sum of a
+  // row's weights, built for edge_weight on a weighted fragment
+  std::vector<eid_t> off;
+  std::vector<vid_t> nbr;  // gids
+  std::vector<float> w, cdf;
+  // seeds this fragment OWNS; nodes[s * row_len + column], gid space,
+  // kInvalidVid for none
+  std::vector<uint64_t> seed_ids;
+  std::vector<vid_t> nodes;
+  // tree nodes currently AT this fragment: (seed index, column, vertex)
+  struct Live {
+    uint64_t seed;
+    uint64_t col;
+    vid_t gid;
+  };
+  std::vector<Live> live;
+
+  void init(const Fragment& frag, const std::vector<oid_t>& seeds,
+            const std::vector<int64_t>& fanouts, SampleStrategy st, int k,
+            uint64_t seed_) {
+    lay = fanout_layout(fanouts, seeds.size());  // throws before any alloc
+    if (st == SampleStrategy::kTopK && k < 1)
+      throw std::runtime_error("sample_neighbors: top_k = " +
+                               std::to_string(k) + " is below 1");
+    strategy = st;
+    top_k = k;
+    seed = seed_;
+    level = 0;
+    seed_ids.clear();
+    live.clear();
+    for (size_t i = 0; i < seeds.size(); ++i) {
+      vid_t lid;
+      if (frag.oid2lid(seeds[i], &lid) && frag.inner(lid)) {
+        seed_ids.push_back(i);
+        live.push_back({i, 0, frag.lid2gid(lid)});
+      }
+    }
+    const uint64_t row_len = lay.row_len();
+    nodes.assign(seed_ids.size() * row_len, kInvalidVid);
+    for (size_t s = 0; s < seed_ids.size(); ++s)
+      nodes[s * row_len] = live[s].gid;
+  }
+
+  void build_rows(const Fragment& frag) {
+    const vid_t iv = frag.ivnum();
+    off.assign(static_cast<size_t>(iv) + 1, 0);
+    for (vid_t v = 0; v < iv; ++v) off[v + 1] = off[v] + frag.out_degree(v);
+    nbr.resize(off[iv]);
+    const bool weighted = frag.has_weights();
+    const bool want_cdf = weighted && strategy == SampleStrategy::kEdgeWeight;
+    if (weighted) w.resize(off[iv]); else w.clear();
+    if (want_cdf) cdf.resize(off[iv]); else cdf.clear();
+    parallel_for(0, iv, [&](size_t vs) {
+      auto adj = frag.out_edges(static_cast<vid_t>(vs));
+      if (adj.n == 0) return;
+      const eid_t b = off[vs];
+      std::vector<std::pair<vid_t, uint32_t>> key(adj.n);
+      for (size_t i = 0; i < adj.n; ++i)
+        key[i] = {frag.lid2gid(adj.dst[i]), static_cast<uint32_t>(i)};
+      std::sort(key.begin(), key.end());
+      float acc = 0.f;
+      for (size_t i = 0; i < adj.n; ++i) {
+        nbr[b + i] = key[i].first;
+        if (weighted) w[b + i] = adj.w[key[i].second];
+        if (want_cdf) cdf[b + i] = acc = acc + w[b + i];
+      }
+    }, 256);
+  }
+
+  // the child that draw r takes from inner vertex lid; kInvalidVid at a
+  // dead end
+  vid_t pick(vid_t lid, uint64_t r) const {
+    const eid_t b = off[lid];
+    const uint64_t deg = off[lid + 1] - b;
+    if (deg == 0) return kInvalidVid;
+    uint64_t slot = 0;
+    if (strategy == SampleStrategy::kRandom ||
+        (strategy == SampleStrategy::kEdgeWeight && cdf.empty())) {
+      slot = fanout_mulhi(r, deg);
+    } else if (strategy == SampleStrategy::kEdgeWeight) {
+      const float* c = cdf.data() + b;
+      const float total = c[deg - 1];
+      if (!(total > 0.f)) return kInvalidVid;
+      const float u =
+          static_cast<float>(static_cast<uint32_t>(r >> 40)) * 0x1p-24f;
+      const float t = u * total;  // one fp32 multiply, rounded to nearest
+      slot = std::upper_bound(c, c + deg, t) - c;
+      if (slot >= deg) slot = deg - 1;
+    } else {
+      const uint64_t k = static_cast<uint64_t>(top_k);
+      const uint64_t kk = std::min<uint64_t>(k, deg);
+      slot = fanout_mulhi(r, kk);
+      if (!w.empty() && deg > k) {
+        // the slot-th heaviest arc, ties to the smaller slot
+        const float* wr = w.data() + b;
+        std::vector<uint32_t> idx(deg);
+        for (uint64_t i = 0; i < deg; ++i) idx[i] = static_cast<uint32_t>(i);
+        std::partial_sort(idx.begin(), idx.begin() + kk, idx.end(),
+                          [&](uint32_t x, uint32_t y) {
+                            if (wr[x] != wr[y]) return wr[x] > wr[y];
+                            return x < y;
+                          });
+        slot = idx[slot];
+      }
+    }
+    return nbr[b + slot];
+  }
+};
+
+class FanoutSamplerApp {
+ public:
+  struct Msg {
+    uint64_t seed;
+    uint64_t col;
+    int32_t record;  // 1 = report to the seed's origin, 0 = expand here
+    vid_t gid;
+  };
+
+  // set by the driver before the query: owner fragment of each seed
+  std::vector<fid_t> origin_map_;
+
+  void PEval(const Fragment& frag, FanoutContext& ctx, MessageManager& mm) {
+    ctx.build_rows(frag);
+    expand(frag, ctx, mm);
+  }
+
+  void IncEval(const Fragment& frag, FanoutContext& ctx,
+               MessageManager& mm) {
+    std::vector<Msg> in;
+    mm.process_raw<Msg>([&](int, vid_t, Msg m) {
+      std::lock_guard<std::mutex> lk(in_mutex_);
+      in.push_back(m);
+    });
+    const uint64_t row_len = ctx.lay.row_len();
+    for (const Msg& m : in) {
+      if (m.record) {
+        ctx.nodes[row_of(ctx, m.seed) * row_len + m.col] = m.gid;
+      } else {
+        ctx.live.push_back({m.seed, m.col, m.gid});
+      }
+    }
+    expand(frag, ctx, mm);
+  }
+
+ private:
+  std::mutex in_mutex_;
+
+  static size_t row_of(const FanoutContext& ctx, uint64_t seed) {
+    return std::lower_bound(ctx.seed_ids.begin(), ctx.seed_ids.end(), seed) -
+           ctx.seed_ids.begin();
+  }
+
+  // one level: every live node draws its children
+  void expand(const Fragment& frag, FanoutContext& ctx, MessageManager& mm) {
+    const int h = ++ctx.level;
+    std::vector<FanoutContext::Live> next;
+    if (h <= ctx.lay.levels()) {
+      const uint64_t f = ctx.lay.fan[h - 1];
+      const uint64_t row_len = ctx.lay.row_len();
+      const bool more = h < ctx.lay.levels();
+      for (const auto& nd : ctx.live) {
+        const vid_t lid = frag.gid2lid(nd.gid);
+        if (lid == kInvalidVid || !frag.inner(lid)) continue;
+        const uint64_t first =
+            ctx.lay.col[h] + (nd.col - ctx.lay.col[h - 1]) * f;
+        const fid_t origin =
+            origin_map_.empty() ? frag.fid() : origin_map_[nd.seed];
+        const size_t row = origin == frag.fid() ? row_of(ctx, nd.seed) : 0;
+        for (uint64_t c = 0; c < f; ++c) {
+          const uint64_t col = first + c;
+          const vid_t child =
+              ctx.pick(lid, fanout_draw(ctx.seed, nd.seed, col - 1));
+          if (child == kInvalidVid) continue;  // dead: the subtree stays -1
+          if (origin == frag.fid())
+            ctx.nodes[row * row_len + col] = child;
+          else
+            mm.send_to_fragment(0, origin, /*routing gid (unused)*/ 0,
+                                Msg{nd.seed, col, 1, child});
+          if (!more) continue;
+          const fid_t owner = frag.parser().fid(child);
+          if (owner == frag.fid())
+            next.push_back({nd.seed, col, child});
+          else
+            mm.send_to_fragment(0, owner, child, Msg{nd.seed, col, 0, child});
+        }
+      }
+    }
+    ctx.live = std::move(next);
+    if (!ctx.live.empty()) mm.force_continue();
+  }
 };
 
 }  // namespace grapehip

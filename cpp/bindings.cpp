@@ -304,7 +304,84 @@ py::dict gpu_dict(const GpuRunResult& r, const PyGraph& pg, bool is_i64,
   }
   return out;
 }
+
+// sample / sample_neighbors: seeds as device ids of the graph as loaded,
+// kSampleNoVertex for one that is no vertex
+std::vector<uint32_t> sample_dev_ids(const PyGraph& g, const DevIdMap& m,
+                                     const arr_i64& oids) {
+  std::vector<uint32_t> dev(oids.size());
+  for (ssize_t i = 0; i < oids.size(); ++i) {
+    int64_t oid = oids.data()[i];
+    uint32_t v = kSampleNoVertex;
+    vid_t gid;
+    if (!m.frag) {
+      if (oid >= 0 && static_cast<uint64_t>(oid) < g.dev->nv_real)
+        v = static_cast<uint32_t>(oid);
+    } else if (m.frag->vm().get_gid(oid, &gid)) {
+      v = m.to_dev(oid);
+    }
+    dev[i] = v;
+  }
+  return dev;
+}
+
+// the [walk_ids.size()][row_len] table of a device sampler run, in oids
+py::array_t<int64_t> sample_table(const GpuRunResult& r, const DevIdMap& m,
+                                  size_t row_len) {
+  size_t n = r.walk_ids.size();
+  py::array_t<int64_t> table({n, row_len});
+  auto* pp = table.mutable_data();
+  for (size_t i = 0; i < n * row_len; ++i)
+    pp[i] = r.paths[i] == kSampleNoVertex ? -1 : m.to_oid(r.paths[i]);
+  return table;
+}
 #endif
+
+SampleStrategy parse_sample_strategy(const std::string& strategy) {
+  if (strategy == "random") return SampleStrategy::kRandom;
+  if (strategy == "edge_weight") return SampleStrategy::kEdgeWeight;
+  if (strategy == "top_k") return SampleStrategy::kTopK;
+  throw std::runtime_error("strategy must be random|edge_weight|top_k");
+}
+
+// Where a sampler call `fn` runs. device unset: the host app wherever it can
+// run, the device otherwise. Throws where the chosen path cannot run.
+bool sample_on_device(const PyEngine& eng, const PyGraph& g,
+                      std::optional<bool> device, const std::string& fn) {
+  bool on_device = device.has_value() ? *device : !g.frag;
+#ifdef GRAPEHIP_WITH_HIP
+  if (!device.has_value() && !(eng.use_gpu && g.dev)) on_device = false;
+#else
+  if (!device.has_value()) on_device = false;
+#endif
+  if (!on_device && !g.frag)
+    throw std::runtime_error(fn + " needs a host fragment");
+  if (on_device) {
+#ifdef GRAPEHIP_WITH_HIP
+    if (!eng.use_gpu || !eng.gpu)
+      throw std::runtime_error(fn +
+                               "(device=True) needs an engine with gpu=True");
+    if (!g.dev)
+      throw std::runtime_error(fn +
+                               "(device=True): the graph has no device graph");
+#else
+    throw std::runtime_error(fn + "(device=True): built without HIP");
+#endif
+  }
+  return on_device;
+}
+
+// owner fragment of every seed of a sampler call (0 for one that is no
+// vertex)
+std::vector<fid_t> sample_origins(const Fragment& frag,
+                                  const std::vector<oid_t>& oids) {
+  std::vector<fid_t> origin(oids.size());
+  for (size_t i = 0; i < oids.size(); ++i) {
+    vid_t gid;
+    origin[i] = frag.vm().get_gid(oids[i], &gid) ? frag.parser().fid(gid) : 0;
+  }
+  return origin;
+}
 
 }  // namespace
 
@@ -429,6 +506,8 @@ PYBIND11_MODULE(_core, m) {
              d["cdf_ms"] = c.cdf_ms;
              d["topk_ms"] = c.topk_ms;
              d["top_k_max"] = kSampleTopKMax;
+             d["fanout_calls"] = c.fanout_calls;
+             d["fanout_draws"] = c.fanout_draws;
              return d;
 #else
              (void)reset;
@@ -1145,48 +1224,12 @@ PYBIND11_MODULE(_core, m) {
               std::optional<bool> device) {
              // device unset: the host app wherever it can run (its results
              // for a seed stay what they were), the device otherwise
-             bool on_device = device.has_value() ? *device : !g.frag;
-#ifdef GRAPEHIP_WITH_HIP
-             if (!device.has_value() && !(eng.use_gpu && g.dev))
-               on_device = false;
-#else
-             if (!device.has_value()) on_device = false;
-#endif
-             if (!on_device && !g.frag)
-               throw std::runtime_error("sample needs a host fragment");
-             SampleStrategy st;
-             if (strategy == "random")
-               st = SampleStrategy::kRandom;
-             else if (strategy == "edge_weight")
-               st = SampleStrategy::kEdgeWeight;
-             else if (strategy == "top_k")
-               st = SampleStrategy::kTopK;
-             else
-               throw std::runtime_error(
-                   "strategy must be random|edge_weight|top_k");
+             const bool on_device = sample_on_device(eng, g, device, "sample");
+             SampleStrategy st = parse_sample_strategy(strategy);
              if (on_device) {
 #ifdef GRAPEHIP_WITH_HIP
-               if (!eng.use_gpu || !eng.gpu)
-                 throw std::runtime_error(
-                     "sample(device=True) needs an engine with gpu=True");
-               if (!g.dev)
-                 throw std::runtime_error(
-                     "sample(device=True): the graph has no device graph");
                DevIdMap m = dev_id_map(g);
-               std::vector<uint32_t> dev_starts(starts.size());
-               for (ssize_t i = 0; i < starts.size(); ++i) {
-                 int64_t oid = starts.data()[i];
-                 uint32_t v = kSampleNoVertex;
-                 vid_t gid;
-                 if (!m.frag) {
-                   if (oid >= 0 &&
-                       static_cast<uint64_t>(oid) < g.dev->nv_real)
-                     v = static_cast<uint32_t>(oid);
-                 } else if (m.frag->vm().get_gid(oid, &gid)) {
-                   v = m.to_dev(oid);
-                 }
-                 dev_starts[i] = v;
-               }
+               std::vector<uint32_t> dev_starts = sample_dev_ids(g, m, starts);
                GpuRunResult r;
                {
                  py::gil_scoped_release rel;
@@ -1194,19 +1237,9 @@ PYBIND11_MODULE(_core, m) {
                                      static_cast<int>(st), top_k, seed);
                }
                py::dict out = gpu_dict(r, g, /*is_i64=*/true, false);
-               size_t n = r.walk_ids.size(), len = hops + 1;
-               py::array_t<int64_t> paths({n, len});
-               auto* pp = paths.mutable_data();
-               for (size_t i = 0; i < n * len; ++i)
-                 pp[i] = r.paths[i] == kSampleNoVertex
-                             ? -1
-                             : m.to_oid(r.paths[i]);
                out["walk_ids"] = to_np(r.walk_ids);
-               out["paths"] = paths;
+               out["paths"] = sample_table(r, m, hops + 1);
                return out;
-#else
-               throw std::runtime_error(
-                   "sample(device=True): built without HIP");
 #endif
              }
              std::vector<oid_t> st_oids(starts.data(),
@@ -1219,14 +1252,7 @@ PYBIND11_MODULE(_core, m) {
                py::gil_scoped_release rel;
                mm.init(eng.c(), g.frag.get(), eng.n_threads);
                ctx.init(*g.frag, st_oids, hops, st, top_k, seed);
-               app.origin_map_.resize(st_oids.size());
-               for (size_t i = 0; i < st_oids.size(); ++i) {
-                 vid_t gid;
-                 app.origin_map_[i] =
-                     g.frag->vm().get_gid(st_oids[i], &gid)
-                         ? g.frag->parser().fid(gid)
-                         : 0;
-               }
+               app.origin_map_ = sample_origins(*g.frag, st_oids);
                RunWorker(app, ctx, *g.frag, mm);
              }
              size_t n = ctx.paths.size();
@@ -1248,6 +1274,70 @@ PYBIND11_MODULE(_core, m) {
              return out;
            },
            py::arg("graph"), py::arg("starts"), py::arg("hops") = 2,
+           py::arg("strategy") = "random", py::arg("top_k") = 4,
+           py::arg("seed") = 7, py::arg("device") = std::nullopt)
+      .def("sample_neighbors",
+           [](PyEngine& eng, PyGraph& g, arr_i64 seeds,
+              const std::vector<int64_t>& fanouts,
+              const std::string& strategy, int top_k, uint64_t seed,
+              std::optional<bool> device) {
+             // routed as sample() is: the host app wherever it can run
+             const bool on_device =
+                 sample_on_device(eng, g, device, "sample_neighbors");
+             SampleStrategy st = parse_sample_strategy(strategy);
+             // a bad fan-out or a table above the cap fails here, before
+             // either path allocates
+             const FanoutLayout lay = fanout_layout(fanouts, seeds.size());
+             const size_t row_len = lay.row_len();
+             py::dict out;
+             if (on_device) {
+#ifdef GRAPEHIP_WITH_HIP
+               DevIdMap m = dev_id_map(g);
+               std::vector<uint32_t> dev_seeds = sample_dev_ids(g, m, seeds);
+               GpuRunResult r;
+               {
+                 py::gil_scoped_release rel;
+                 r = eng.gpu->sample_neighbors(*g.dev, dev_seeds, fanouts,
+                                               static_cast<int>(st), top_k,
+                                               seed);
+               }
+               out = gpu_dict(r, g, /*is_i64=*/true, false);
+               out["seed_ids"] = to_np(r.walk_ids);
+               out["nodes"] = sample_table(r, m, row_len);
+#endif
+             } else {
+               std::vector<oid_t> oids(seeds.data(),
+                                       seeds.data() + seeds.size());
+               FanoutSamplerApp app;
+               FanoutContext ctx;
+               MessageManager mm;
+               {
+                 py::gil_scoped_release rel;
+                 ctx.init(*g.frag, oids, fanouts, st, top_k, seed);
+                 mm.init(eng.c(), g.frag.get(), eng.n_threads);
+                 app.origin_map_ = sample_origins(*g.frag, oids);
+                 RunWorker(app, ctx, *g.frag, mm);
+               }
+               size_t n = ctx.seed_ids.size();
+               py::array_t<int64_t> ids(n);
+               py::array_t<int64_t> nodes({n, row_len});
+               for (size_t i = 0; i < n; ++i)
+                 ids.mutable_data()[i] = static_cast<int64_t>(ctx.seed_ids[i]);
+               auto* pp = nodes.mutable_data();
+               for (size_t i = 0; i < n * row_len; ++i)
+                 pp[i] = ctx.nodes[i] == kInvalidVid
+                             ? -1
+                             : g.frag->vm().get_oid(ctx.nodes[i]);
+               out["seed_ids"] = ids;
+               out["nodes"] = nodes;
+             }
+             py::array_t<int64_t> offs(lay.col.size());
+             for (size_t h = 0; h < lay.col.size(); ++h)
+               offs.mutable_data()[h] = static_cast<int64_t>(lay.col[h]);
+             out["level_offsets"] = offs;
+             return out;
+           },
+           py::arg("graph"), py::arg("seeds"), py::arg("fanouts"),
            py::arg("strategy") = "random", py::arg("top_k") = 4,
            py::arg("seed") = 7, py::arg("device") = std::nullopt)
       .def("sssp_auto",

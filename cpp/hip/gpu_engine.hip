@@ -7942,6 +7942,42 @@ struct SampleIndex {
 
 enum { kSampleRandom = 0, kSampleEdgeWeight = 1, kSampleTopK = 2 };
 
+// The slot that draw r takes out of the stored row `row` = arcs
+// [b, b + deg), deg >= 1; deg itself at a dead end. The one pick rule of the
+// walk step and of the fan-out level kernel.
+template <int STRAT>
+__device__ __forceinline__ uint64_t sample_pick(const SampleIndex& ix,
+                                                uint32_t row, uint64_t b,
+                                                uint64_t deg, uint64_t r) {
+  uint64_t pick = deg;
+  if constexpr (STRAT == kSampleRandom) {
+    pick = __umul64hi(r, deg);
+  } else if constexpr (STRAT == kSampleEdgeWeight) {
+    const float* __restrict__ c = ix.cdf + b;
+    const float total = c[deg - 1];
+    if (total > 0.f) {
+      const float u =
+          static_cast<float>(static_cast<uint32_t>(r >> 40)) * 0x1p-24f;
+      const float t = __fmul_rn(u, total);
+      uint64_t lo = 0, hi = deg;
+      while (lo < hi) {
+        uint64_t mid = (lo + hi) >> 1;
+        if (c[mid] <= t)
+          lo = mid + 1;
+        else
+          hi = mid;
+      }
+      pick = lo < deg ? lo : deg - 1;
+    }
+  } else {
+    const uint64_t kk = deg < ix.k ? deg : ix.k;
+    pick = __umul64hi(r, kk);
+    if (ix.topk_slots && deg > ix.k)
+      pick = ix.topk_slots[ix.topk_rank[row] * ix.k + pick];
+  }
+  return pick;
+}
+
 // One lane per live walker of `cur`; `more`: hops remain after this one.
 template <int STRAT>
 __global__ void sample_step_kernel(DevGraphView g,
@@ -7967,32 +8003,8 @@ __global__ void sample_step_kernel(DevGraphView g,
       const uint64_t deg = here ? g.oe_off[row + 1] - b : 0;
       if (deg) {
         const uint64_t r = sample_draw(seed, wk.walk, hop);
-        uint64_t pick = deg;  // deg: dead end
-        if constexpr (STRAT == kSampleRandom) {
-          pick = __umul64hi(r, deg);
-        } else if constexpr (STRAT == kSampleEdgeWeight) {
-          const float* __restrict__ c = ix.cdf + b;
-          const float total = c[deg - 1];
-          if (total > 0.f) {
-            const float u =
-                static_cast<float>(static_cast<uint32_t>(r >> 40)) * 0x1p-24f;
-            const float t = __fmul_rn(u, total);
-            uint64_t lo = 0, hi = deg;
-            while (lo < hi) {
-              uint64_t mid = (lo + hi) >> 1;
-              if (c[mid] <= t)
-                lo = mid + 1;
-              else
-                hi = mid;
-            }
-            pick = lo < deg ? lo : deg - 1;
-          }
-        } else {
-          const uint64_t kk = deg < ix.k ? deg : ix.k;
-          pick = __umul64hi(r, kk);
-          if (ix.topk_slots && deg > ix.k)
-            pick = ix.topk_slots[ix.topk_rank[row] * ix.k + pick];
-        }
+        const uint64_t pick =
+            sample_pick<STRAT>(ix, row, b, deg, r);  // deg: dead end
         if (pick < deg) {
           const uint32_t nv = g.oe_dst[b + pick];
           paths[static_cast<uint64_t>(wk.walk) * row_len + hop + 1] = nv;
@@ -8026,6 +8038,110 @@ __global__ void sample_gather_kernel(const uint32_t* __restrict__ paths,
                        i % row_len];
     if (inv && x != kSampleNoVertex) x = inv[x];
     out[i] = x;
+  }
+}
+
+// --- fan-out (neighbourhood) sampling ---------------------------------------
+//
+// Reference parity: examples/gnn_sampler --hop_and_num f_1-...-f_H: f_1
+// neighbours of every seed, f_2 of each of those, ..., with replacement. The
+// tree of seed i is level-major on the device: level h is one array of
+// n * L_h ids (L_0 = 1, L_h = L_{h-1} * f_h), entry i * L_h + j being slot
+// base_h + j of seed i (base_h = L_1 + ... + L_{h-1}). Item t of level h has
+// its parent at t / f_h of level h - 1 and writes entry t: the f_h lanes of
+// one parent are adjacent, read one parent entry and one pair of row offsets,
+// and the child writes are coalesced. No queue, no append. The draw of item t
+// is sample_draw(seed, t / L_h, base_h + t % L_h), the pick sample_pick.
+// Every array is prefilled with kSampleNoVertex, so a dead parent leaves its
+// subtree dead, and the owner of the parent's vertex alone writes: an
+// element-wise min over ranks completes a level.
+
+// a / d; `small`: both fit in 32 bits (one hardware-assisted divide)
+__device__ __forceinline__ uint64_t fanout_div(uint64_t a, uint64_t d,
+                                               bool small) {
+  return small ? static_cast<uint32_t>(a) / static_cast<uint32_t>(d) : a / d;
+}
+
+// level 0: the seeds in stored ids, on every rank alike
+__global__ void fanout_seed_kernel(const uint32_t* __restrict__ seeds,
+                                   uint64_t n,
+                                   const uint32_t* __restrict__ perm,
+                                   uint32_t nv_global,
+                                   uint32_t* __restrict__ level0) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < n; i += stride) {
+    uint32_t v = seeds[i];
+    if (v < nv_global) {
+      if (perm) v = perm[v];
+    } else {
+      v = kSampleNoVertex;
+    }
+    level0[i] = v;
+  }
+}
+
+// One lane per item of a level of n_items = n * L entries, fan-out f over
+// `parents` (the level before, n_items / f entries); cnt: the draws made.
+template <int STRAT>
+__global__ void fanout_level_kernel(DevGraphView g,
+                                    const uint32_t* __restrict__ parents,
+                                    uint32_t* __restrict__ level,
+                                    uint64_t n_items, uint32_t f, uint64_t L,
+                                    uint64_t base_pos, SampleIndex ix,
+                                    uint64_t seed,
+                                    unsigned long long* __restrict__ cnt) {
+  const uint32_t lane = threadIdx.x & 63;
+  const uint64_t stride = static_cast<uint64_t>(gridDim.x) * blockDim.x;
+  const bool small = n_items <= 0xFFFFFFFFull;  // L and f are no larger
+  for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                       (threadIdx.x - lane);
+       base < n_items; base += stride) {
+    const uint64_t t = base + lane;
+    bool drew = false;
+    if (t < n_items) {
+      const uint32_t pv = parents[fanout_div(t, f, small)];
+      if (pv != kSampleNoVertex && g.is_owned(pv)) {
+        const uint32_t row = g.row(pv);
+        const uint64_t b = g.oe_off[row];
+        const uint64_t deg = g.oe_off[row + 1] - b;
+        if (deg) {
+          const uint64_t i = fanout_div(t, L, small);
+          const uint64_t r = sample_draw(seed, i, base_pos + (t - i * L));
+          const uint64_t pick = sample_pick<STRAT>(ix, row, b, deg, r);
+          if (pick < deg) {
+            level[t] = g.oe_dst[b + pick];
+            drew = true;
+          }
+        }
+      }
+    }
+    const unsigned long long dm = __ballot(drew);
+    if (lane == 0 && dm)
+      atomicAdd(cnt, static_cast<unsigned long long>(__popcll(dm)));
+  }
+}
+
+// level-major to root-major: columns [col0, col0 + L) of the rows of the
+// owned seeds, hub renumbering undone
+__global__ void fanout_gather_kernel(const uint32_t* __restrict__ level,
+                                     const uint32_t* __restrict__ own,
+                                     uint64_t n_own, uint64_t L,
+                                     uint64_t row_len, uint64_t col0,
+                                     const uint32_t* __restrict__ inv,
+                                     uint32_t* __restrict__ out) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  const uint64_t total = n_own * L;
+  const bool small = total <= 0xFFFFFFFFull;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < total; i += stride) {
+    const uint64_t r = fanout_div(i, L, small);
+    const uint64_t j = i - r * L;
+    uint32_t x = level[static_cast<uint64_t>(own[r]) * L + j];
+    if (inv && x != kSampleNoVertex) x = inv[x];
+    out[r * row_len + col0 + j] = x;
   }
 }
 
@@ -8285,11 +8401,141 @@ GpuRunResult GpuContext::sample(DeviceGraph& g,
   return res;
 }
 
+namespace {
+
+template <int STRAT>
+void launch_fanout_level(hipStream_t s, const DevGraphView& view,
+                         const uint32_t* parents, uint32_t* level,
+                         uint64_t n_items, uint32_t f, uint64_t L,
+                         uint64_t base_pos, const SampleIndex& ix,
+                         uint64_t seed, unsigned long long* cnt) {
+  fanout_level_kernel<STRAT><<<grid_for(n_items), kBlock, 0, s>>>(
+      view, parents, level, n_items, f, L, base_pos, ix, seed, cnt);
+}
+
+}  // namespace
+
+GpuRunResult GpuContext::sample_neighbors(DeviceGraph& g,
+                                          const std::vector<uint32_t>& seeds,
+                                          const std::vector<int64_t>& fanouts,
+                                          int strategy, int top_k,
+                                          uint64_t seed) {
+  RangeMarker _mk("grapehip::sample_neighbors");
+  auto& I = *impl_;
+  hipStream_t s = I.compute;
+  if (strategy < kSampleRandom || strategy > kSampleTopK)
+    throw std::runtime_error("sample_neighbors: strategy must be 0, 1 or 2");
+  if (strategy == kSampleTopK && (top_k < 1 || top_k > kSampleTopKMax))
+    throw std::runtime_error("sample_neighbors: top_k = " +
+                             std::to_string(top_k) + " is outside 1.." +
+                             std::to_string(kSampleTopKMax) +
+                             " (kSampleTopKMax) of the device sampler");
+  const uint64_t n = seeds.size();
+  // sizes checked in 64 bits before anything is allocated
+  const FanoutLayout lay = fanout_layout(fanouts, n);
+  const int H = lay.levels();
+  const uint64_t row_len = lay.row_len();
+  const bool multi = world_ > 1;
+  // every weight of an unweighted graph is 1
+  if (strategy == kSampleEdgeWeight && !g.weighted) strategy = kSampleRandom;
+  SampleIndex ix{nullptr, nullptr, nullptr, static_cast<uint32_t>(top_k)};
+  if (strategy == kSampleEdgeWeight) {
+    ensure_sample_cdf(g, I, s);
+    ix.cdf = g.sample_cdf.data();
+  } else if (strategy == kSampleTopK && g.weighted) {
+    ensure_sample_topk(g, I, top_k, s);
+    ix.topk_rank = g.sample_topk_rank.data();
+    ix.topk_slots = g.sample_topk_slots.data();
+  }
+
+  // the seeds owned here, by the ids as loaded (the hub renumbering keeps
+  // the owner), and the live parents of level 1
+  std::vector<uint32_t> own;
+  uint64_t live = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    if (seeds[i] >= g.nv_global) continue;
+    ++live;
+    if (seeds[i] >= g.v_begin && seeds[i] < g.v_end)
+      own.push_back(static_cast<uint32_t>(i));
+  }
+
+  // workspace shared with sample(): the levels lie one after the other in
+  // sample_paths, level h at n * col[h]
+  const uint64_t cap = n ? n : 1;
+  const size_t n_cnt = static_cast<size_t>(H) + 1;
+  grow(I.sample_paths, cap * row_len);
+  grow(I.sample_starts, cap);
+  grow(I.sample_cnt, n_cnt);
+  grow(I.sample_own, own.size() ? own.size() : 1);
+  grow(I.sample_out, own.size() ? own.size() * row_len : 1);
+  DevGraphView view = make_view(g, rank_, world_);
+  uint32_t* levels = I.sample_paths.data();
+
+  RunBracket br(I, comm_);
+
+  uint64_t draws = 0;
+  int rounds = 0;
+  if (n) {
+    HIP_CHECK(hipMemcpyAsync(I.sample_starts.data(), seeds.data(), n * 4,
+                             hipMemcpyHostToDevice, s));
+    fill(levels, kSampleNoVertex, n * row_len, s);
+    HIP_CHECK(hipMemsetAsync(I.sample_cnt.data(), 0, n_cnt * 8, s));
+    fanout_seed_kernel<<<grid_for(n), kBlock, 0, s>>>(
+        I.sample_starts.data(), n, g.permuted ? g.perm.data() : nullptr,
+        g.nv_global, levels);
+    auto launch = strategy == kSampleRandom
+                      ? launch_fanout_level<kSampleRandom>
+                      : (strategy == kSampleEdgeWeight
+                             ? launch_fanout_level<kSampleEdgeWeight>
+                             : launch_fanout_level<kSampleTopK>);
+    for (int h = 1; h <= H && live; ++h) {
+      ++rounds;
+      const uint64_t L = lay.len[h];
+      uint32_t* level = levels + n * lay.col[h];
+      launch(s, view, levels + n * lay.col[h - 1], level, n * L,
+             static_cast<uint32_t>(lay.fan[h - 1]), L, lay.col[h] - 1, ix,
+             seed, I.sample_cnt.data() + h);
+      // the one count read per level
+      unsigned long long c = 0;
+      HIP_CHECK(hipMemcpyAsync(&c, I.sample_cnt.data() + h, 8,
+                               hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      live = multi ? comm_->allreduce_sum(static_cast<uint64_t>(c)) : c;
+      draws += live;
+      // each entry was written by at most one rank over 0xFFFFFFFF
+      if (multi && live) I.dc.allreduce_min_u32(level, n * L, s);
+    }
+  }
+  std::vector<uint32_t> rows_h;
+  if (!own.empty()) {
+    HIP_CHECK(hipMemcpyAsync(I.sample_own.data(), own.data(), own.size() * 4,
+                             hipMemcpyHostToDevice, s));
+    for (int h = 0; h <= H; ++h)
+      fanout_gather_kernel<<<grid_for(own.size() * lay.len[h]), kBlock, 0,
+                             s>>>(
+          levels + n * lay.col[h], I.sample_own.data(), own.size(),
+          lay.len[h], row_len, lay.col[h],
+          g.permuted ? g.inv.data() : nullptr, I.sample_out.data());
+    rows_h.resize(own.size() * row_len);
+    HIP_CHECK(hipMemcpyAsync(rows_h.data(), I.sample_out.data(),
+                             rows_h.size() * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  ++I.sample_dbg.fanout_calls;
+  I.sample_dbg.fanout_draws = draws;
+  GpuRunResult res = br.finish(rounds, draws);
+  res.paths = std::move(rows_h);
+  res.walk_ids.assign(own.begin(), own.end());
+  return res;
+}
+
 GpuContext::SampleDebug GpuContext::debug_sample(bool reset) {
   SampleDebug out = impl_->sample_dbg;
   if (reset)
     impl_->sample_dbg.calls = impl_->sample_dbg.cdf_builds =
-        impl_->sample_dbg.topk_builds = impl_->sample_dbg.steps = 0;
+        impl_->sample_dbg.topk_builds = impl_->sample_dbg.steps =
+            impl_->sample_dbg.fanout_calls = impl_->sample_dbg.fanout_draws =
+                0;
   return out;
 }
 

@@ -11,6 +11,7 @@
 #include <memory>
 #include <vector>
 
+#include "../core/fanout.hpp"
 #include "../core/fragment.hpp"
 #include "../core/net.hpp"
 #include "../core/types.hpp"
@@ -204,6 +205,18 @@ class GpuContext {
   // that still had a live walk; traversed_edges: steps taken, global.
   GpuRunResult sample(DeviceGraph& g, const std::vector<uint32_t>& starts,
                       int hops, int strategy, int top_k, uint64_t seed);
+  // fan-out (neighbourhood) sampling on the stored out-CSR: fanouts[0]
+  // neighbours of every seed, fanouts[1] of each of those, ..., drawn with
+  // replacement by the draw and pick rule of sample() with the sample slot
+  // in place of the hop (core/fanout.hpp has the layout). seeds as `starts`
+  // of sample(). walk_ids: the owned seeds; paths: their rows,
+  // [walk_ids.size()][1 + S], 0xFFFFFFFF below a dead end. rounds: levels
+  // that began with a live parent somewhere; traversed_edges: samples
+  // drawn, global. Throws on a table above kFanoutMaxEntries.
+  GpuRunResult sample_neighbors(DeviceGraph& g,
+                                const std::vector<uint32_t>& seeds,
+                                const std::vector<int64_t>& fanouts,
+                                int strategy, int top_k, uint64_t seed);
 
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device
@@ -231,9 +244,11 @@ class GpuContext {
   std::array<uint64_t, 6> debug_kclique(bool reset = false);
   // test hook: device sample() calls, cdf and top-k index builds so far,
   // the steps of the last call, and the bytes and build time of the last
-  // index built of each kind. reset zeroes the counts after the read.
+  // index built of each kind; sample_neighbors() calls and the draws of the
+  // last one. reset zeroes the counts after the read.
   struct SampleDebug {
     uint64_t calls = 0, cdf_builds = 0, topk_builds = 0, steps = 0;
+    uint64_t fanout_calls = 0, fanout_draws = 0;
     uint64_t cdf_bytes = 0, topk_bytes = 0;
     double cdf_ms = 0, topk_ms = 0;
   };

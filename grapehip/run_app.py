@@ -58,6 +58,9 @@ def build_parser():
                     choices=("random", "edge_weight", "top_k"))
     ap.add_argument("--sample_top_k", type=int, default=4)
     ap.add_argument("--sample_seed", type=int, default=7)
+    ap.add_argument("--sample_fanout", default="",
+                    help="fan-out sampling instead of walks: neighbours per "
+                         "level, e.g. 4-5 (reference --hop_and_num)")
     # delta mutation (LoadGraphAndMutate, loader.h:55-68 +
     # ev_fragment_mutator.h: base graph + additions/removals files)
     ap.add_argument("--efile_add", default="")
@@ -169,6 +172,13 @@ def main(argv=None):
         res = eng.core_decomposition(g)
     elif app == "kclique":
         res = eng.kclique(g, args.kclique_k)
+    elif app == "sample" and args.sample_fanout:
+        # the tree of every seed as one row; --gpu as for the walks
+        res = eng.sample_neighbors(
+            g, np.arange(args.sample_walks, dtype=np.int64),
+            [int(f) for f in args.sample_fanout.split("-")],
+            strategy=args.sample_strategy, top_k=args.sample_top_k,
+            seed=args.sample_seed, device=args.gpu)
     elif app == "sample":
         # --gpu walks on the device; without it the host app runs
         res = eng.sample(g, np.arange(args.sample_walks, dtype=np.int64),
@@ -187,6 +197,10 @@ def main(argv=None):
             if app == "kclique":
                 if rank == 0:
                     f.write("%d\n" % res["clique_count"])
+            elif app == "sample" and args.sample_fanout:
+                # one line per owned seed: the seed and its S samples
+                for row in res["nodes"]:
+                    f.write(" ".join(map(str, row)) + "\n")
             elif app == "sample":
                 # one line per owned walk: walk_id v0 v1 ...
                 for wid, path in zip(res["walk_ids"], res["paths"]):

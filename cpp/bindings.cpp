@@ -461,6 +461,22 @@ PYBIND11_MODULE(_core, m) {
 #endif
            },
            py::arg("reset") = false)
+      .def("_debug_pr_epilogue",
+           [](PyEngine& e, bool reset) {
+#ifdef GRAPEHIP_WITH_HIP
+             if (!e.gpu) throw std::runtime_error("no gpu engine");
+             auto c = e.gpu->debug_pr_epilogue(reset);
+             py::dict d;
+             d["calls"] = c[0];
+             d["replayed"] = c[1];
+             return d;
+#else
+             (void)reset;
+             throw std::runtime_error("no hip");
+             return py::dict();
+#endif
+           },
+           py::arg("reset") = false)
       .def("_debug_arc_depth",
            [](PyEngine& e) {
 #ifdef GRAPEHIP_WITH_HIP

@@ -1301,6 +1301,23 @@ __global__ void pr_contrib_kernel(const double* __restrict__ rank,
   }
 }
 
+// The per-iteration scalar, a row's new rank and its next contribution. One
+// text each for pr_fused_apply_kernel and the pull epilogues, so that the
+// contraction into fused multiply-adds cannot differ between the two paths.
+__device__ __forceinline__ double pr_base_of(double damping, double inv_n,
+                                             double dangling) {
+  return (1.0 - damping) * inv_n + damping * dangling * inv_n;
+}
+
+__device__ __forceinline__ double pr_new_rank(double base, double damping,
+                                              double sum) {
+  return base + damping * sum;
+}
+
+__device__ __forceinline__ float pr_contrib_of(double nv, uint64_t deg) {
+  return static_cast<float>(nv / static_cast<double>(deg));
+}
+
 __global__ void pr_apply_kernel(double* __restrict__ rank,
                                 const double* __restrict__ acc,
                                 const double* __restrict__ dangling,
@@ -1354,21 +1371,20 @@ __global__ void pr_fused_apply_kernel(
     double* __restrict__ dangling_next, double* __restrict__ l1_delta) {
   __shared__ double s_wave[kBlock / kWave];
   __shared__ double s_dang[kBlock / kWave];
-  const double base =
-      (1.0 - damping) * inv_n + damping * (*dangling_cur) * inv_n;
+  const double base = pr_base_of(damping, inv_n, *dangling_cur);
   double d1 = 0, dang = 0;
   size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
                     threadIdx.x;
        i < nrows; i += stride) {
     uint32_t r = rows[i];
-    double nv = base + damping * acc[v_begin + r];
+    double nv = pr_new_rank(base, damping, acc[v_begin + r]);
     if (l1_delta) d1 += fabs(nv - rank[v_begin + r]);
     rank[v_begin + r] = nv;
     if (r < owned_real) {
       uint64_t deg = off[r + 1] - off[r];
       if (deg) {
-        contrib[r] = static_cast<float>(nv / static_cast<double>(deg));
+        contrib[r] = pr_contrib_of(nv, deg);
       } else {
         contrib[r] = 0.0f;
         dang += nv;
@@ -1421,6 +1437,66 @@ __global__ void pr_dangling_kernel(const double* __restrict__ rank,
 #pragma unroll
     for (int w = 0; w < kBlock / kWave; ++w) t += s_wave[w];
     unsafeAtomicAdd(out, t);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// PageRank epilogues (undirected graph, single GPU, fixed iterations; see
+// GpuContext::pagerank_epilogue and KERNELS.md). A pull that has a row's sum
+// in hand applies it on the spot instead of storing it to acc for
+// pr_fused_apply_kernel to read back: EPI 0 stores the sum (every other
+// path), EPI 1 writes the row's next contribution, EPI 2, on the last
+// iteration, its rank. Every active row of an undirected graph has a pull
+// edge, so none is dangling and the dangling sum is the isolated rows'
+// alone: a scalar recurrence, stepped by one thread.
+// ---------------------------------------------------------------------------
+struct PrEpilogue {
+  const double* base;   // pr_epi_scal + 1, written by pr_epi_scalar_kernel
+  double damping;
+  float* contrib_next;  // by stored id, EPI 1
+  double* rank;         // by stored id, EPI 2
+};
+
+template <int EPI>
+__device__ __forceinline__ void pr_row_done(const PrEpilogue& ep, double base,
+                                            uint32_t v, double sum,
+                                            uint64_t deg) {
+  const double nv = pr_new_rank(base, ep.damping, sum);
+  if (EPI == 1) ep.contrib_next[v] = pr_contrib_of(nv, deg);
+  else ep.rank[v] = nv;
+}
+
+// sc: [0]=dangling sum, [1]=base, [2]=previous base. What thread 0 of
+// pr_fused_apply_kernel does with the isolated rows, and nothing else.
+__global__ void pr_epi_scalar_kernel(double* __restrict__ sc, double inv_n,
+                                     double damping, double n_isolated) {
+  const double base = pr_base_of(damping, inv_n, sc[0]);
+  sc[1] = base;
+  sc[0] = n_isolated * base;
+  sc[2] = base;
+}
+
+// Start of a call: every rank is 1/N, so the dangling sum is a count times
+// 1/N and a row's contribution is (1/N)/deg.
+__global__ void pr_epi_init_kernel(double* __restrict__ sc, double dangling0,
+                                   double inv_n) {
+  sc[0] = dangling0;
+  sc[1] = inv_n;
+  sc[2] = inv_n;
+}
+
+__global__ void pr_epi_contrib0_kernel(const uint32_t* __restrict__ rows,
+                                       uint64_t nrows,
+                                       const uint64_t* __restrict__ off,
+                                       double inv_n, uint32_t v_begin,
+                                       float* __restrict__ contrib) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       i < nrows; i += stride) {
+    const uint32_t r = rows[i];
+    const uint64_t deg = off[r + 1] - off[r];
+    contrib[v_begin + r] = deg ? pr_contrib_of(inv_n, deg) : 0.0f;
   }
 }
 
@@ -1763,19 +1839,18 @@ __global__ void gather_row_deg_kernel(const uint64_t* __restrict__ off,
 
 // PageRank epilogue of the fused path: every owned row outside rows_active
 // (isolated, padding included as before) takes the last iteration's base.
-// Tests the degree offsets instead of keeping a list of the isolated rows
-// (296M entries at the benchmark shape).
+// Tests the row's bit in the active-row bitmap that the buckets keep
+// (DeviceGraph::active_bm) instead of keeping a list of the isolated rows
+// (296M entries at the benchmark shape) or reading two offsets per row.
 __global__ void pr_fill_isolated_kernel(
-    const uint64_t* __restrict__ off, const uint64_t* __restrict__ out_off,
-    uint32_t owned, uint32_t v_begin, const double* __restrict__ last_base,
-    double* __restrict__ rank) {
+    const uint32_t* __restrict__ active_bm, uint32_t owned, uint32_t v_begin,
+    const double* __restrict__ last_base, double* __restrict__ rank) {
   const double base = *last_base;
   size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (uint64_t r = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
                     threadIdx.x;
        r < owned; r += stride)
-    if (!row_has_edges(off, out_off, static_cast<uint32_t>(r)))
-      rank[v_begin + r] = base;
+    if (!((active_bm[r >> 5] >> (r & 31)) & 1u)) rank[v_begin + r] = base;
 }
 
 // Phase-split pulls (multi-GPU compute/comm overlap): the per-row
@@ -1821,16 +1896,21 @@ __device__ __forceinline__ PrSpan pr_span(const uint32_t* __restrict__ dst,
 // lengths, then sweeps the chunk's edges with CONSECUTIVE lanes on
 // consecutive edge slots (coalesced dst/contrib streams), wave-segmented
 // sums per row and LDS fp64 accumulation at run tails.
-template <int PHASE>
+// EPI 1, 2 (PHASE 0 only): the thread that would store the row's sum applies
+// it instead (pr_row_done); the row length it staged is the row's degree.
+template <int PHASE, int EPI = 0>
 __global__ void pr_pull_small_cm_kernel(
     const uint64_t* __restrict__ off, const uint32_t* __restrict__ dst,
     const float* __restrict__ contrib, const uint32_t* __restrict__ rows,
     uint64_t nrows, uint32_t v_begin, uint32_t lo, uint32_t hi,
-    double* __restrict__ acc) {
+    double* __restrict__ acc, PrEpilogue ep) {
+  static_assert(EPI == 0 || PHASE == 0, "epilogues need the whole row");
   __shared__ uint64_t s_b1[kBlock], s_b2[kBlock];
   __shared__ uint32_t s_n1[kBlock], s_pref[kBlock + 1];
   __shared__ double s_acc[kBlock];
   const int lane = threadIdx.x & 63;
+  double ep_base = 0.0;
+  if constexpr (EPI != 0) ep_base = *ep.base;
   for (uint64_t chunk = static_cast<uint64_t>(blockIdx.x) * kBlock;
        chunk < nrows;
        chunk += static_cast<uint64_t>(gridDim.x) * kBlock) {
@@ -1900,7 +1980,9 @@ __global__ void pr_pull_small_cm_kernel(
     __syncthreads();
     if (i < nrows) {
       uint32_t r = rows[i];
-      if (PHASE == 2) acc[v_begin + r] += s_acc[threadIdx.x];
+      if constexpr (EPI != 0)
+        pr_row_done<EPI>(ep, ep_base, v_begin + r, s_acc[threadIdx.x], n);
+      else if (PHASE == 2) acc[v_begin + r] += s_acc[threadIdx.x];
       else acc[v_begin + r] = s_acc[threadIdx.x];
     }
     __syncthreads();
@@ -2345,13 +2427,20 @@ pr_pull_seg_kernel(PrSegView v, const uint32_t* __restrict__ dst,
 
 // Folds a row's partials in (segment, item) order: a lane per row, and the
 // whole wave, in a fixed tree, for a row with more than 64 of them.
+// EPI 1, 2: the lane that would store the row's sum applies it instead
+// (pr_row_done), with the row's degree from row_deg.
+template <int EPI = 0>
 __global__ void pr_seg_reduce_kernel(const uint32_t* __restrict__ rows,
                                      const uint64_t* __restrict__ row_first,
                                      uint64_t nrows,
                                      const double* __restrict__ part,
                                      uint32_t v_begin,
-                                     double* __restrict__ acc) {
+                                     double* __restrict__ acc,
+                                     const uint32_t* __restrict__ row_deg,
+                                     PrEpilogue ep) {
   const int lane = threadIdx.x & 63;
+  double ep_base = 0.0;
+  if constexpr (EPI != 0) ep_base = *ep.base;
   size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
   for (uint64_t j0 = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
                      (threadIdx.x - lane);
@@ -2378,7 +2467,29 @@ __global__ void pr_seg_reduce_kernel(const uint32_t* __restrict__ rows,
       t = __shfl(t, 0, 64);
       if (lane == l) sum = t;
     }
-    if (j < nrows) acc[v_begin + rows[j]] = sum;
+    if (j < nrows) {
+      if constexpr (EPI != 0)
+        pr_row_done<EPI>(ep, ep_base, v_begin + rows[j], sum, row_deg[j]);
+      else
+        acc[v_begin + rows[j]] = sum;
+    }
+  }
+}
+
+// The degrees of the id-segment rows, for the reduce's epilogue. A row of
+// 2^32 arcs or more raises *too_long.
+__global__ void pr_seg_row_deg_kernel(const uint64_t* __restrict__ off,
+                                      const uint32_t* __restrict__ rows,
+                                      uint64_t nrows,
+                                      uint32_t* __restrict__ deg,
+                                      int* __restrict__ too_long) {
+  size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+  for (uint64_t j = static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                    threadIdx.x;
+       j < nrows; j += stride) {
+    const uint64_t d = off[rows[j] + 1] - off[rows[j]];
+    if (d > 0xFFFFFFFFull) *too_long = 1;
+    deg[j] = static_cast<uint32_t>(d);
   }
 }
 
@@ -2850,6 +2961,9 @@ struct GpuContext::Impl {
   // pagerank() calls through the id-segment pull [0] and the row-tier
   // pulls [1] (test hook, see debug_pr_path)
   uint64_t pr_path_counts[2] = {0, 0};
+  // pagerank() calls on the epilogue path [0], their iterations replayed
+  // from a captured hipGraph [1] (test hook, see debug_pr_epilogue)
+  uint64_t pr_epi_counts[2] = {0, 0};
   // device kclique() calls so far, and the rows of the last one in the
   // wave, block and global tiers (test hook, see debug_kclique)
   uint64_t kclique_calls = 0;
@@ -2973,6 +3087,8 @@ DeviceGraph::~DeviceGraph() {
   if (pr_graph_exec)
     (void)hipGraphExecDestroy(
         reinterpret_cast<hipGraphExec_t>(pr_graph_exec));
+  for (void* e : pr_epi_exec)
+    if (e) (void)hipGraphExecDestroy(reinterpret_cast<hipGraphExec_t>(e));
 }
 
 GpuContext::GpuContext(TcpComm* comm, int rank, int world)
@@ -3064,6 +3180,23 @@ std::array<uint64_t, 2> GpuContext::debug_pr_path(bool reset) {
   std::array<uint64_t, 2> out = {impl_->pr_path_counts[0],
                                  impl_->pr_path_counts[1]};
   if (reset) impl_->pr_path_counts[0] = impl_->pr_path_counts[1] = 0;
+  return out;
+}
+
+// GRAPEHIP_PR_EPILOGUE: 0 keeps pagerank() off the epilogue path, read once
+// per process.
+static bool pr_epilogue_on() {
+  static const bool on = [] {
+    const char* e = getenv("GRAPEHIP_PR_EPILOGUE");
+    return !e || !*e || atoi(e) != 0;
+  }();
+  return on;
+}
+
+std::array<uint64_t, 2> GpuContext::debug_pr_epilogue(bool reset) {
+  std::array<uint64_t, 2> out = {impl_->pr_epi_counts[0],
+                                 impl_->pr_epi_counts[1]};
+  if (reset) impl_->pr_epi_counts[0] = impl_->pr_epi_counts[1] = 0;
   return out;
 }
 
@@ -3529,11 +3662,16 @@ static void ensure_buckets(DeviceGraph& g, GpuContext::Impl& I,
   // rows_active: bitmap of rows with an edge, compacted in ascending order
   g.n_active = owned - g.n_isolated_real - g.n_isolated_pad;
   g.rows_active.resize(g.n_active ? g.n_active : 1);
+  // the bitmap stays on the graph (pr_fill_isolated_kernel tests it)
+  size_t nwords = (static_cast<size_t>(owned) + 31) / 32;
+  g.active_bm.resize(nwords ? nwords : 1);
+  active_rows_bitmap_kernel<<<grid_for(nwords), kBlock, 0, s>>>(
+      pull_off, out_off, owned, g.active_bm.data(), nwords);
   if (g.n_active) {
-    size_t nwords = (static_cast<size_t>(owned) + 31) / 32;
+    // compact_frontier clears the bitmap it reads: give it a copy
     DeviceBuffer<uint32_t> bm(nwords);
-    active_rows_bitmap_kernel<<<grid_for(nwords), kBlock, 0, s>>>(
-        pull_off, out_off, owned, bm.data(), nwords);
+    HIP_CHECK(hipMemcpyAsync(bm.data(), g.active_bm.data(), nwords * 4,
+                             hipMemcpyDeviceToDevice, s));
     uint64_t got =
         compact_frontier(I, bm.data(), owned, 0, g.rows_active.data(), s);
     HIP_CHECK(hipStreamSynchronize(s));  // bm is freed on return
@@ -3672,6 +3810,10 @@ static bool ensure_pr_segments(DeviceGraph& g, GpuContext::Impl& I,
   pr_seg_cut_kernel<<<grid_for(nrows * kWave), kBlock, 0, s>>>(
       pull_off, pull_dst, g.seg_rows.data(), nrows, bnd, len.data(),
       too_long.data());
+  g.seg_row_deg.resize(nrows);
+  pr_seg_row_deg_kernel<<<grid_for(nrows), kBlock, 0, s>>>(
+      pull_off, g.seg_rows.data(), nrows, g.seg_row_deg.data(),
+      too_long.data());
   if (too_long.download(s)[0]) return false;
   exclusive_scan(len.data(), pref.data(), n, s, I.scan);
   pr_seg_pieces_kernel<<<grid_for(n), kBlock, 0, s>>>(
@@ -3720,7 +3862,7 @@ static bool ensure_pr_segments(DeviceGraph& g, GpuContext::Impl& I,
             (unsigned long)nrows, (unsigned long)g.n_seg_spans,
             (unsigned long)g.n_seg_parts, (unsigned long)K.head,
             (unsigned long)K.ids, K.item, g.pr_seg_build_ms,
-            (g.n_seg_spans * 24.0 + g.n_seg_parts * 8.0 + nrows * 12.0) / 1e6);
+            (g.n_seg_spans * 24.0 + g.n_seg_parts * 8.0 + nrows * 16.0) / 1e6);
     for (int k = 0; k < kPrSegs; ++k) fprintf(stderr, " %u", v.n_items[k]);
     fprintf(stderr, "\n");
   }
@@ -3750,7 +3892,7 @@ GpuContext::PrSegDebug GpuContext::debug_pr_segments(DeviceGraph& g) {
   d.row_first = g.seg_row_first.download(s);
   d.build_ms = g.pr_seg_build_ms;
   d.bytes = g.n_seg_spans * 24 + 8 + g.n_seg_parts * 8 +
-            g.n_seg_rows * 12 + 8;
+            g.n_seg_rows * 16 + 8;
   return d;
 }
 
@@ -4611,6 +4753,143 @@ GpuRunResult GpuContext::sssp(DeviceGraph& g, int64_t source,
 // ---------------------------------------------------------------------------
 // PageRank (push + fp64 hw atomics; reduce-scatter/allgather over xGMI)
 // ---------------------------------------------------------------------------
+
+// The id-segment pull of one iteration: item counters to zero, then the
+// persistent kernel at the arc depth in effect. The reduce follows it.
+static void launch_pr_pull_seg(DeviceGraph& g, GpuContext::Impl& I,
+                               const uint32_t* pull_dst, const float* contrib,
+                               hipStream_t s) {
+  g.seg_ctr.zero(s);
+  const int grid = I.num_cus * kPrSegBlocksPerCu;
+  auto pull_seg = [&](auto depth) {
+    constexpr int D = decltype(depth)::value;
+    if (pr_seg_knobs().nt)
+      pr_pull_seg_kernel<true, D><<<grid, kBlock, 0, s>>>(
+          g.seg_view, pull_dst, contrib, g.seg_ctr.data(), g.seg_part.data());
+    else
+      pr_pull_seg_kernel<false, D><<<grid, kBlock, 0, s>>>(
+          g.seg_view, pull_dst, contrib, g.seg_ctr.data(), g.seg_part.data());
+  };
+  switch (arc_depth()) {
+    case 4: pull_seg(std::integral_constant<int, 4>{}); break;
+    case 2: pull_seg(std::integral_constant<int, 2>{}); break;
+    default: pull_seg(std::integral_constant<int, 1>{});
+  }
+}
+
+// The epilogue path: pull direction, single GPU, not tiled, undirected,
+// tol <= 0, iters >= 1 (pagerank() decides). Against the fused path it
+// drops, per iteration, the acc round trip, pr_fused_apply_kernel, nine of
+// ten rank writes and the dangling pair's memset, atomics and copy; per
+// call, the fills of rank and acc and the passes over all owned rows that
+// found the dangling sum and the first contributions. The sums, their
+// order and the fp64 expressions are the fused path's; only the first
+// dangling value differs, n * (1/N) instead of an atomic sum of n copies
+// of 1/N.
+GpuRunResult GpuContext::pagerank_epilogue(DeviceGraph& g, double damping,
+                                           int iters, bool seg, bool fetch) {
+  auto& I = *impl_;
+  hipStream_t s = I.compute;
+  const uint32_t nv_pad = padded_nv(g, world_);
+  const uint32_t owned = g.owned();
+  const double inv_n = 1.0 / static_cast<double>(g.nv_real);
+  const double n_iso = static_cast<double>(g.n_isolated_real);
+  const uint64_t* off = g.oe_off.data();
+  const uint32_t* dst = g.oe_dst.data();
+  ++I.pr_epi_counts[0];
+
+  // on the DeviceGraph: the captured hipGraphs bake these pointers
+  if (g.pr_contrib2.size() < nv_pad) g.pr_contrib2.resize(nv_pad);
+  if (g.pr_epi_scal.size() < 3) g.pr_epi_scal.resize(3);
+  float* const buf[2] = {g.pr_contrib.data(), g.pr_contrib2.data()};
+  double* const sc = g.pr_epi_scal.data();
+  double* const rank = g.pr_rank.data();
+
+  RunBracket br(I, comm_);
+
+  // Every owned row's rank is written below: the active rows' by the last
+  // iteration, the others' by pr_fill_isolated_kernel. The rows of the
+  // buffer outside the owned range keep the 1/N that the fused path's fill
+  // leaves there.
+  fill(rank, inv_n, g.v_begin, s);
+  fill(rank + g.v_begin + owned, inv_n, nv_pad - g.v_begin - owned, s);
+  pr_epi_init_kernel<<<1, 1, 0, s>>>(sc, n_iso * inv_n, inv_n);
+  if (g.n_active)
+    pr_epi_contrib0_kernel<<<grid_for(g.n_active), kBlock, 0, s>>>(
+        g.rows_active.data(), g.n_active, off, inv_n, g.v_begin, buf[0]);
+
+  // one iteration: the scalar step, then the pulls with their epilogues
+  auto iteration = [&](const float* cin, float* cout, bool last) {
+    pr_epi_scalar_kernel<<<1, 1, 0, s>>>(sc, inv_n, damping, n_iso);
+    const PrEpilogue ep{sc + 1, damping, cout, rank};
+    auto launch = [&](auto tag) {
+      constexpr int E = decltype(tag)::value;
+      if (g.n_small)
+        pr_pull_small_cm_kernel<0, E>
+            <<<grid_for(g.n_small), kBlock, 0, s>>>(
+                off, dst, cin, g.rows_small.data(), g.n_small, g.v_begin,
+                g.v_begin, g.v_end, nullptr, ep);
+      if (seg) {
+        launch_pr_pull_seg(g, I, dst, cin, s);
+        pr_seg_reduce_kernel<E><<<grid_for(g.n_seg_rows), kBlock, 0, s>>>(
+            g.seg_rows.data(), g.seg_row_first.data(), g.n_seg_rows,
+            g.seg_part.data(), g.v_begin, nullptr, g.seg_row_deg.data(), ep);
+      }
+    };
+    if (last) launch(std::integral_constant<int, 2>{});
+    else launch(std::integral_constant<int, 1>{});
+  };
+
+  // Iterations but the last: captured once per (graph, damping) as two
+  // hipGraphs, buf[0] -> buf[1] and back, and replayed alternately; as for
+  // the fused path, a graph's first call records them on the stream
+  // instead. The last iteration, which writes rank, is always recorded.
+  const bool capture = g.pr_calls++ > 0 && iters > 1;
+  hipGraphExec_t exec[2] = {
+      reinterpret_cast<hipGraphExec_t>(g.pr_epi_exec[0]),
+      reinterpret_cast<hipGraphExec_t>(g.pr_epi_exec[1])};
+  if (capture && (!exec[0] || g.pr_epi_damping != damping)) {
+    for (int k = 0; k < 2; ++k) {
+      if (exec[k]) HIP_CHECK(hipGraphExecDestroy(exec[k]));
+      exec[k] = nullptr;
+      g.pr_epi_exec[k] = nullptr;
+    }
+    for (int k = 0; k < 2; ++k) {
+      hipGraph_t graph = nullptr;
+      HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+      iteration(buf[k], buf[k ^ 1], false);
+      HIP_CHECK(hipStreamEndCapture(s, &graph));
+      HIP_CHECK(hipGraphInstantiate(&exec[k], graph, nullptr, nullptr, 0));
+      HIP_CHECK(hipGraphDestroy(graph));
+      g.pr_epi_exec[k] = exec[k];
+    }
+    g.pr_epi_damping = damping;
+  }
+
+  for (int it = 0; it + 1 < iters; ++it) {
+    if (capture) {
+      HIP_CHECK(hipGraphLaunch(exec[it & 1], s));
+      ++I.pr_epi_counts[1];
+    } else {
+      iteration(buf[it & 1], buf[(it & 1) ^ 1], false);
+    }
+  }
+  iteration(buf[(iters - 1) & 1], buf[iters & 1], true);
+  pr_fill_isolated_kernel<<<grid_for(owned), kBlock, 0, s>>>(
+      g.active_bm.data(), owned, g.v_begin, sc + 2, rank);
+
+  GpuRunResult res =
+      br.finish(iters, static_cast<uint64_t>(iters) * g.total_edges);
+  if (fetch) {
+    res.f64.resize(owned);
+    HIP_CHECK(hipMemcpyAsync(res.f64.data(), rank + g.v_begin,
+                             static_cast<size_t>(owned) * 8,
+                             hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  return res;
+}
+
 GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
                                   int iters, double tol, bool fetch) {
   RangeMarker _mk("grapehip::pagerank");
@@ -4654,10 +4933,18 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
   // pointers (locals would dangle across calls — GPU fault under realloc)
   if (g.pr_rank.size() < nv_pad) {
     g.pr_rank.resize(nv_pad);
-    g.pr_acc.resize(nv_pad);
     g.pr_contrib.resize(nv_pad);
     g.pr_dangling.resize(3);
   }
+  // Epilogue path (KERNELS.md "PageRank epilogues"): the pulls apply their
+  // row sums themselves. It has the small and the id-segment pull; a graph
+  // whose mid and hub rows go through the row-tier pulls stays on the fused
+  // path, as do directed graphs and tol > 0.
+  if (pr_epilogue_on() && pull && !multi && !tiled && !g.directed &&
+      tol <= 0 && iters >= 1 && (seg || (!g.n_mid && !g.n_large)))
+    return pagerank_epilogue(g, damping, iters, seg, fetch);
+  // no sum goes through acc on the epilogue path: allocated here only
+  if (g.pr_acc.size() < nv_pad) g.pr_acc.resize(nv_pad);
   DeviceBuffer<double>& rank_arr = g.pr_rank;
   DeviceBuffer<double>& acc = g.pr_acc;
   DeviceBuffer<float>& contrib = g.pr_contrib;
@@ -4685,31 +4972,15 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
       if (g.n_small)
         pr_pull_small_cm_kernel<P><<<grid_for(g.n_small), kBlock, 0, s>>>(
             pull_off, pull_dst, contrib.data(), g.rows_small.data(),
-            g.n_small, g.v_begin, g.v_begin, g.v_end, acc.data());
+            g.n_small, g.v_begin, g.v_begin, g.v_end, acc.data(),
+            PrEpilogue{});
       if (seg) {
         // P == 0 here. Every partial is stored by the pull and read by the
         // reduce; the kernel boundary carries them across the XCDs.
-        g.seg_ctr.zero(s);
-        const int grid = I.num_cus * kPrSegBlocksPerCu;
-        auto pull_seg = [&](auto depth) {
-          constexpr int D = decltype(depth)::value;
-          if (pr_seg_knobs().nt)
-            pr_pull_seg_kernel<true, D><<<grid, kBlock, 0, s>>>(
-                g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
-                g.seg_part.data());
-          else
-            pr_pull_seg_kernel<false, D><<<grid, kBlock, 0, s>>>(
-                g.seg_view, pull_dst, contrib.data(), g.seg_ctr.data(),
-                g.seg_part.data());
-        };
-        switch (arc_depth()) {
-          case 4: pull_seg(std::integral_constant<int, 4>{}); break;
-          case 2: pull_seg(std::integral_constant<int, 2>{}); break;
-          default: pull_seg(std::integral_constant<int, 1>{});
-        }
-        pr_seg_reduce_kernel<<<grid_for(g.n_seg_rows), kBlock, 0, s>>>(
+        launch_pr_pull_seg(g, I, pull_dst, contrib.data(), s);
+        pr_seg_reduce_kernel<0><<<grid_for(g.n_seg_rows), kBlock, 0, s>>>(
             g.seg_rows.data(), g.seg_row_first.data(), g.n_seg_rows,
-            g.seg_part.data(), g.v_begin, acc.data());
+            g.seg_part.data(), g.v_begin, acc.data(), nullptr, PrEpilogue{});
         return;
       }
       if (g.n_mid)
@@ -4915,7 +5186,7 @@ GpuRunResult GpuContext::pagerank(DeviceGraph& g, double damping,
   // complete the device-resident result (outside the captured graph)
   if (fused)
     pr_fill_isolated_kernel<<<grid_for(owned), kBlock, 0, s>>>(
-        pull_off, g.oe_off.data(), owned, g.v_begin, d_dangling.data() + 2,
+        g.active_bm.data(), owned, g.v_begin, d_dangling.data() + 2,
         rank_arr.data());
   GpuRunResult res =
       br.finish(rounds, static_cast<uint64_t>(iters) * g.total_edges);

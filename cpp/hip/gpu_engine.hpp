@@ -51,6 +51,9 @@ struct DeviceGraph {
   // counted in n_isolated_real.
   DeviceBuffer<uint32_t> rows_active;
   uint64_t n_active = 0, n_isolated_real = 0, n_isolated_pad = 0;
+  // the same set as a bitmap over the owned rows (bit r % 32 of word r / 32),
+  // kept for pr_fill_isolated_kernel: one bit per row instead of two offsets
+  DeviceBuffer<uint32_t> active_bm;
   // hub work list: every rows_large row cut into kHubSeg-arc items, in row
   // order. hub_item_row[i] indexes rows_large, hub_item_seg[i] is the
   // segment within the row, hub_row_first[j] the first item of row j
@@ -71,6 +74,9 @@ struct DeviceGraph {
   DeviceBuffer<uint32_t> seg_rows, seg_span_row, seg_span_slot, seg_ctr;
   DeviceBuffer<uint64_t> seg_span_pref, seg_span_base, seg_row_first;
   DeviceBuffer<double> seg_part;
+  // arcs of seg_rows[j], for the reduce's epilogue (KERNELS.md "PageRank
+  // epilogues"): 4 B per row, read in row order
+  DeviceBuffer<uint32_t> seg_row_deg;
   uint64_t n_seg_rows = 0, n_seg_spans = 0, n_seg_parts = 0;
   uint32_t seg_bound[kPrSegs + 1] = {};
   PrSegView seg_view{};
@@ -116,6 +122,17 @@ struct DeviceGraph {
   // pr_dangling: [0]=current dangling sum, [1]=next, [2]=previous base
   DeviceBuffer<double> pr_rank, pr_acc, pr_dangling;
   DeviceBuffer<float> pr_contrib;
+  // Epilogue path (pagerank_epilogue; undirected, single GPU, fixed
+  // iterations): the pulls apply the row sum themselves, so an iteration
+  // gathers from one contribution buffer and writes the other. pr_contrib2
+  // is allocated when the path first runs, pr_acc only when another path
+  // does. pr_epi_scal: [0]=dangling sum, [1]=base of the iteration,
+  // [2]=previous base. pr_epi_exec: the captured iteration pr_contrib ->
+  // pr_contrib2 [0] and back [1]; neither writes pr_rank.
+  DeviceBuffer<float> pr_contrib2;
+  DeviceBuffer<double> pr_epi_scal;
+  void* pr_epi_exec[2] = {nullptr, nullptr};
+  double pr_epi_damping = 0.0;
   // random-walk sampler indexes (built lazily by sample(), kept with the
   // graph). sample_cdf: inclusive fp32 prefix sum of the weights inside each
   // stored out-row, 4 B per stored arc (edge_weight on weighted graphs).
@@ -235,6 +252,10 @@ class GpuContext {
   // the id-segment pull [0] or the row-tier pulls [1] (single-GPU row pull
   // only; the tiled and multi-GPU paths count as neither)
   std::array<uint64_t, 2> debug_pr_path(bool reset = false);
+  // test hook: pagerank() calls so far that took the epilogue path [0] and
+  // the iterations of those calls that were replayed from a captured
+  // hipGraph [1] (GRAPEHIP_PR_EPILOGUE, read once per process)
+  std::array<uint64_t, 2> debug_pr_epilogue(bool reset = false);
   // test hook: the arc depth in effect (GRAPEHIP_ARC_DEPTH, read once per
   // process; KERNELS.md "Arc depth")
   int debug_arc_depth();
@@ -288,6 +309,9 @@ class GpuContext {
  private:
   // shared peeling driver: all levels (coreness) or the single level k - 1
   GpuRunResult peel(DeviceGraph& g, bool all_levels, int k, bool fetch);
+  // pagerank() on the epilogue path; seg: the id-segment pull is on for g
+  GpuRunResult pagerank_epilogue(DeviceGraph& g, double damping, int iters,
+                                 bool seg, bool fetch);
   std::unique_ptr<Impl> impl_;
   TcpComm* comm_;
   int rank_, world_, dev_ = 0;

@@ -264,7 +264,8 @@ class SamplerApp {
 // Fan-out (neighbourhood) sampling, CPU path. Reference parity:
 // examples/gnn_sampler --hop_and_num f_1-...-f_H (sampler.h hop_size /
 // next_pos): f_1 neighbours of every seed, f_2 of each of those, ..., with
-// replacement, one flat row of 1 + S ids per seed (core/fanout.hpp).
+// replacement, or as distinct arcs of the parent (replace = false), one flat
+// row of 1 + S ids per seed (core/fanout.hpp).
 //
 // The draws are those of the device path (hip/gpu_engine.hip sample_draw and
 // sample_pick), so host, device and the NumPy oracle agree entry for entry:
@@ -292,6 +293,7 @@ struct FanoutContext {
   SampleStrategy strategy = SampleStrategy::kRandom;
   int top_k = 4;
   uint64_t seed = 7;
+  bool replace = true;  // false: distinct arc slots per parent
   FanoutLayout lay;
   int level = 0;  // the level the live nodes sit on
   // the out-rows of the inner vertices in stored order (ascending gid,
@@ -314,14 +316,18 @@ struct FanoutContext {
 
   void init(const Fragment& frag, const std::vector<oid_t>& seeds,
             const std::vector<int64_t>& fanouts, SampleStrategy st, int k,
-            uint64_t seed_) {
+            uint64_t seed_, bool replace_ = true) {
     lay = fanout_layout(fanouts, seeds.size());  // throws before any alloc
+    if (!replace_)
+      fanout_check_no_replace(st == SampleStrategy::kEdgeWeight &&
+                              frag.has_weights());
     if (st == SampleStrategy::kTopK && k < 1)
       throw std::runtime_error("sample_neighbors: top_k = " +
                                std::to_string(k) + " is below 1");
     strategy = st;
     top_k = k;
     seed = seed_;
+    replace = replace_;
     level = 0;
     seed_ids.clear();
     live.clear();
@@ -402,6 +408,51 @@ struct FanoutContext {
     }
     return nbr[b + slot];
   }
+
+  // replace = false: the f children of inner vertex lid together, children
+  // [c] = kInvalidVid for none (core/fanout.hpp has the rule); draw_of(c) is
+  // the draw of child c's sample slot
+  template <typename Draw>
+  void pick_distinct(vid_t lid, uint64_t f, Draw draw_of,
+                     std::vector<vid_t>& children) const {
+    children.assign(f, kInvalidVid);
+    const eid_t b = off[lid];
+    const uint64_t deg = off[lid + 1] - b;
+    uint64_t m = deg;
+    // the domain: element e is slot order[e], or slot e where order is empty
+    std::vector<uint32_t> order;
+    if (strategy == SampleStrategy::kTopK) {
+      const uint64_t k = static_cast<uint64_t>(top_k);
+      m = std::min<uint64_t>(k, deg);
+      if (!w.empty() && deg > k) {
+        const float* wr = w.data() + b;
+        order.resize(deg);
+        for (uint64_t i = 0; i < deg; ++i) order[i] = static_cast<uint32_t>(i);
+        std::partial_sort(order.begin(), order.begin() + m, order.end(),
+                          [&](uint32_t x, uint32_t y) {
+                            if (wr[x] != wr[y]) return wr[x] > wr[y];
+                            return x < y;
+                          });
+      }
+    }
+    auto element = [&](uint64_t e) {
+      return nbr[b + (order.empty() ? e : order[e])];
+    };
+    if (m <= f) {
+      for (uint64_t c = 0; c < m; ++c) children[c] = element(c);
+      return;
+    }
+    // Floyd's subset sampling in child order
+    std::vector<uint64_t> taken(f);
+    for (uint64_t c = 0; c < f; ++c) {
+      const uint64_t J = m - f + c;
+      const uint64_t t = fanout_mulhi(draw_of(c), J + 1);
+      const bool seen =
+          std::find(taken.begin(), taken.begin() + c, t) != taken.begin() + c;
+      taken[c] = seen ? J : t;
+      children[c] = element(taken[c]);
+    }
+  }
 };
 
 class FanoutSamplerApp {
@@ -451,6 +502,7 @@ class FanoutSamplerApp {
   void expand(const Fragment& frag, FanoutContext& ctx, MessageManager& mm) {
     const int h = ++ctx.level;
     std::vector<FanoutContext::Live> next;
+    std::vector<vid_t> children;  // of one parent, replace = false
     if (h <= ctx.lay.levels()) {
       const uint64_t f = ctx.lay.fan[h - 1];
       const uint64_t row_len = ctx.lay.row_len();
@@ -463,10 +515,16 @@ class FanoutSamplerApp {
         const fid_t origin =
             origin_map_.empty() ? frag.fid() : origin_map_[nd.seed];
         const size_t row = origin == frag.fid() ? row_of(ctx, nd.seed) : 0;
+        if (!ctx.replace)
+          ctx.pick_distinct(lid, f, [&](uint64_t c) {
+            return fanout_draw(ctx.seed, nd.seed, first + c - 1);
+          }, children);
         for (uint64_t c = 0; c < f; ++c) {
           const uint64_t col = first + c;
           const vid_t child =
-              ctx.pick(lid, fanout_draw(ctx.seed, nd.seed, col - 1));
+              ctx.replace
+                  ? ctx.pick(lid, fanout_draw(ctx.seed, nd.seed, col - 1))
+                  : children[c];
           if (child == kInvalidVid) continue;  // dead: the subtree stays -1
           if (origin == frag.fid())
             ctx.nodes[row * row_len + col] = child;

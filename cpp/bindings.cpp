@@ -1296,7 +1296,7 @@ PYBIND11_MODULE(_core, m) {
            [](PyEngine& eng, PyGraph& g, arr_i64 seeds,
               const std::vector<int64_t>& fanouts,
               const std::string& strategy, int top_k, uint64_t seed,
-              std::optional<bool> device) {
+              std::optional<bool> device, bool replace) {
              // routed as sample() is: the host app wherever it can run
              const bool on_device =
                  sample_on_device(eng, g, device, "sample_neighbors");
@@ -1305,6 +1305,14 @@ PYBIND11_MODULE(_core, m) {
              // either path allocates
              const FanoutLayout lay = fanout_layout(fanouts, seeds.size());
              const size_t row_len = lay.row_len();
+             if (!replace) {
+               bool weighted = g.frag && g.frag->has_weights();
+#ifdef GRAPEHIP_WITH_HIP
+               if (on_device) weighted = g.dev->weighted;
+#endif
+               fanout_check_no_replace(st == SampleStrategy::kEdgeWeight &&
+                                       weighted);
+             }
              py::dict out;
              if (on_device) {
 #ifdef GRAPEHIP_WITH_HIP
@@ -1315,7 +1323,7 @@ PYBIND11_MODULE(_core, m) {
                  py::gil_scoped_release rel;
                  r = eng.gpu->sample_neighbors(*g.dev, dev_seeds, fanouts,
                                                static_cast<int>(st), top_k,
-                                               seed);
+                                               seed, replace);
                }
                out = gpu_dict(r, g, /*is_i64=*/true, false);
                out["seed_ids"] = to_np(r.walk_ids);
@@ -1329,7 +1337,7 @@ PYBIND11_MODULE(_core, m) {
                MessageManager mm;
                {
                  py::gil_scoped_release rel;
-                 ctx.init(*g.frag, oids, fanouts, st, top_k, seed);
+                 ctx.init(*g.frag, oids, fanouts, st, top_k, seed, replace);
                  mm.init(eng.c(), g.frag.get(), eng.n_threads);
                  app.origin_map_ = sample_origins(*g.frag, oids);
                  RunWorker(app, ctx, *g.frag, mm);
@@ -1355,7 +1363,8 @@ PYBIND11_MODULE(_core, m) {
            },
            py::arg("graph"), py::arg("seeds"), py::arg("fanouts"),
            py::arg("strategy") = "random", py::arg("top_k") = 4,
-           py::arg("seed") = 7, py::arg("device") = std::nullopt)
+           py::arg("seed") = 7, py::arg("device") = std::nullopt,
+           py::arg("replace") = true)
       .def("sssp_auto",
            [](PyEngine& eng, PyGraph& g, int64_t source) {
              if (!g.frag)

@@ -20,6 +20,31 @@ namespace grapehip {
 // 2^31 ids are 8 GiB of device ids per rank and 16 GiB of int64 on the host
 constexpr uint64_t kFanoutMaxEntries = 1ull << 31;
 
+// Without replacement (replace=False) a live parent fills its f children
+// from its *domain*, an ordered list of m arc slots of its stored out-row:
+// the whole row in stored order (random; edge_weight without weights), or
+// the min(deg, top_k) heaviest arcs, heaviest first, ties to the smaller slot
+// (top_k). m <= f: child c < m takes domain element c, the others stay
+// empty, no draw is used. m > f: Floyd's subset sampling in child order, with
+// r_c the draw of child c's sample slot and index(r, n) = (r * n) >> 64:
+//   J = m - f + c;  t = index(r_c, J + 1);
+//   e_c = J if t is among e_0 .. e_{c-1}, else t;  child c takes element e_c.
+// The e_c are distinct and every f-subset of the domain is equally likely.
+
+// largest fan-out of the device path without replacement: one wave holds the
+// picks of a parent
+constexpr uint64_t kFanoutNoReplaceMax = 64;
+
+// Weighted draws without replacement are not built; `weighted_draw`:
+// strategy edge_weight on a graph that has weights.
+inline void fanout_check_no_replace(bool weighted_draw) {
+  if (weighted_draw)
+    throw std::runtime_error(
+        "sample_neighbors: strategy edge_weight with replace=False is not "
+        "supported on a weighted graph (use random or top_k, or "
+        "replace=True)");
+}
+
 struct FanoutLayout {
   std::vector<uint64_t> fan;  // [H] f_h
   std::vector<uint64_t> len;  // [H + 1] L_h

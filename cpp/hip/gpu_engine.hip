@@ -8394,6 +8394,81 @@ __global__ void fanout_level_kernel(DevGraphView g,
   }
 }
 
+// Without replacement (core/fanout.hpp has the rule): one group of W lanes
+// per parent, W = 1 << log_w the smallest power of two >= f <= 64, lane c of
+// the group its child c, 64 / W parents per wave. A parent's domain is its m
+// arc slots (random: the row, top_k: the min(deg, k) heaviest). m <= f: child
+// c < m is domain element c. m > f: Floyd's subset sampling in child order,
+// step s broadcasting t_s = index(r_s, m - f + s + 1) from lane s to the
+// group and lane s taking m - f + s where a lane below holds t_s already.
+// Every lane of the wave runs all f steps, whatever its group is, so the
+// shuffles and ballots are wave-wide; dead, foreign, short and tail groups
+// only vote false.
+template <int STRAT>
+__global__ void fanout_level_norep_kernel(
+    DevGraphView g, const uint32_t* __restrict__ parents,
+    uint32_t* __restrict__ level, uint64_t n_items, uint32_t f,
+    uint32_t log_w, uint64_t L, uint64_t base_pos, SampleIndex ix,
+    uint64_t seed, unsigned long long* __restrict__ cnt) {
+  static_assert(STRAT == kSampleRandom || STRAT == kSampleTopK,
+                "no cdf rule without replacement");
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t w = 1u << log_w;
+  const uint32_t c = lane & (w - 1);   // child of the group's parent
+  const uint32_t first = lane - c;     // the group's lane 0
+  const unsigned long long gmask =
+      (w == 64 ? ~0ull : (1ull << w) - 1) << first;
+  const bool small = n_items <= 0xFFFFFFFFull;  // L and f are no larger
+  const uint64_t n_par = fanout_div(n_items, f, small);
+  const uint64_t Lp = fanout_div(L, f, small);  // parents per seed
+  const uint64_t stride =
+      (static_cast<uint64_t>(gridDim.x) * blockDim.x) >> log_w;
+  for (uint64_t base = (static_cast<uint64_t>(blockIdx.x) * blockDim.x +
+                        (threadIdx.x - lane)) >> log_w;
+       base < n_par; base += stride) {
+    const uint64_t p = base + (lane >> log_w);
+    uint32_t row = 0;
+    uint64_t b = 0, deg = 0, m = 0, t = 0;
+    if (p < n_par) {
+      const uint32_t pv = parents[p];
+      if (pv != kSampleNoVertex && g.is_owned(pv)) {
+        row = g.row(pv);
+        b = g.oe_off[row];
+        deg = g.oe_off[row + 1] - b;
+        m = deg;
+        if constexpr (STRAT == kSampleTopK) m = deg < ix.k ? deg : ix.k;
+      }
+    }
+    const bool floyd = m > f;  // the same in every lane of a group
+    if (floyd && c < f) {
+      const uint64_t i = fanout_div(p, Lp, small);
+      const uint64_t r =
+          sample_draw(seed, i, base_pos + (p - i * Lp) * f + c);
+      t = __umul64hi(r, m - f + c + 1);
+    }
+    uint64_t e = c;  // m <= f: domain element c
+    for (uint32_t s = 0; s < f; ++s) {
+      const uint64_t ts = __shfl(static_cast<unsigned long long>(t),
+                                 static_cast<int>(first + s), 64);
+      const unsigned long long taken =
+          __ballot(floyd && c < s && e == ts) & gmask;
+      if (floyd && c == s) e = taken ? m - f + s : ts;
+    }
+    const bool drew = c < f && (floyd || c < m);
+    if (drew) {
+      uint64_t slot = e;
+      if constexpr (STRAT == kSampleTopK) {
+        if (ix.topk_slots && deg > ix.k)
+          slot = ix.topk_slots[ix.topk_rank[row] * ix.k + slot];
+      }
+      level[p * f + c] = g.oe_dst[b + slot];
+    }
+    const unsigned long long dm = __ballot(drew);
+    if (lane == 0 && dm)
+      atomicAdd(cnt, static_cast<unsigned long long>(__popcll(dm)));
+  }
+}
+
 // level-major to root-major: columns [col0, col0 + L) of the rows of the
 // owned seeds, hub renumbering undone
 __global__ void fanout_gather_kernel(const uint32_t* __restrict__ level,
@@ -8684,13 +8759,28 @@ void launch_fanout_level(hipStream_t s, const DevGraphView& view,
       view, parents, level, n_items, f, L, base_pos, ix, seed, cnt);
 }
 
+// one group of the smallest power of two >= f lanes per parent
+template <int STRAT>
+void launch_fanout_level_norep(hipStream_t s, const DevGraphView& view,
+                               const uint32_t* parents, uint32_t* level,
+                               uint64_t n_items, uint32_t f, uint64_t L,
+                               uint64_t base_pos, const SampleIndex& ix,
+                               uint64_t seed, unsigned long long* cnt) {
+  uint32_t log_w = 0;
+  while ((1u << log_w) < f) ++log_w;  // f <= kFanoutNoReplaceMax = 64
+  fanout_level_norep_kernel<STRAT>
+      <<<grid_for((n_items / f) << log_w), kBlock, 0, s>>>(
+          view, parents, level, n_items, f, log_w, L, base_pos, ix, seed,
+          cnt);
+}
+
 }  // namespace
 
 GpuRunResult GpuContext::sample_neighbors(DeviceGraph& g,
                                           const std::vector<uint32_t>& seeds,
                                           const std::vector<int64_t>& fanouts,
                                           int strategy, int top_k,
-                                          uint64_t seed) {
+                                          uint64_t seed, bool replace) {
   RangeMarker _mk("grapehip::sample_neighbors");
   auto& I = *impl_;
   hipStream_t s = I.compute;
@@ -8709,6 +8799,17 @@ GpuRunResult GpuContext::sample_neighbors(DeviceGraph& g,
   const bool multi = world_ > 1;
   // every weight of an unweighted graph is 1
   if (strategy == kSampleEdgeWeight && !g.weighted) strategy = kSampleRandom;
+  if (!replace) {
+    fanout_check_no_replace(strategy == kSampleEdgeWeight);
+    // one wave holds the picks of a parent
+    for (uint64_t f : lay.fan)
+      if (f > kFanoutNoReplaceMax)
+        throw std::runtime_error(
+            "sample_neighbors: fanout = " + std::to_string(f) +
+            " is above " + std::to_string(kFanoutNoReplaceMax) +
+            " (kFanoutNoReplaceMax) of the device sampler with "
+            "replace=False");
+  }
   SampleIndex ix{nullptr, nullptr, nullptr, static_cast<uint32_t>(top_k)};
   if (strategy == kSampleEdgeWeight) {
     ensure_sample_cdf(g, I, s);
@@ -8759,6 +8860,10 @@ GpuRunResult GpuContext::sample_neighbors(DeviceGraph& g,
                       : (strategy == kSampleEdgeWeight
                              ? launch_fanout_level<kSampleEdgeWeight>
                              : launch_fanout_level<kSampleTopK>);
+    if (!replace)
+      launch = strategy == kSampleRandom
+                   ? launch_fanout_level_norep<kSampleRandom>
+                   : launch_fanout_level_norep<kSampleTopK>;
     for (int h = 1; h <= H && live; ++h) {
       ++rounds;
       const uint64_t L = lay.len[h];

@@ -230,10 +230,15 @@ class GpuContext {
   // [walk_ids.size()][1 + S], 0xFFFFFFFF below a dead end. rounds: levels
   // that began with a live parent somewhere; traversed_edges: samples
   // drawn, global. Throws on a table above kFanoutMaxEntries.
+  // replace = false: the children of a parent are distinct arc slots, all of
+  // its domain where that is no longer than the fan-out (core/fanout.hpp has
+  // the rule). random and top_k only: edge_weight on a weighted graph throws,
+  // and so does a fan-out above kFanoutNoReplaceMax.
   GpuRunResult sample_neighbors(DeviceGraph& g,
                                 const std::vector<uint32_t>& seeds,
                                 const std::vector<int64_t>& fanouts,
-                                int strategy, int top_k, uint64_t seed);
+                                int strategy, int top_k, uint64_t seed,
+                                bool replace = true);
 
   void device_sync();
   // test hook: exclusive scan of host u32 data on the device

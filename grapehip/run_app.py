@@ -61,6 +61,9 @@ def build_parser():
     ap.add_argument("--sample_fanout", default="",
                     help="fan-out sampling instead of walks: neighbours per "
                          "level, e.g. 4-5 (reference --hop_and_num)")
+    ap.add_argument("--sample_replace", type=int, default=1, choices=(0, 1),
+                    help="with --sample_fanout: 0 draws the children of a "
+                         "parent without replacement")
     # delta mutation (LoadGraphAndMutate, loader.h:55-68 +
     # ev_fragment_mutator.h: base graph + additions/removals files)
     ap.add_argument("--efile_add", default="")
@@ -178,7 +181,8 @@ def main(argv=None):
             g, np.arange(args.sample_walks, dtype=np.int64),
             [int(f) for f in args.sample_fanout.split("-")],
             strategy=args.sample_strategy, top_k=args.sample_top_k,
-            seed=args.sample_seed, device=args.gpu)
+            seed=args.sample_seed, device=args.gpu,
+            replace=bool(args.sample_replace))
     elif app == "sample":
         # --gpu walks on the device; without it the host app runs
         res = eng.sample(g, np.arange(args.sample_walks, dtype=np.int64),

@@ -16,6 +16,9 @@ calls only.
 Seeds are uniform over the vertex ids, the same list for both paths. Prints
 one JSON line per graph and workload. Under rocprofv3 use --repeat 1 --no-host
 and read the fanout_level_kernel dispatches in start order: one per level.
+
+--no-replace: every call with replace=False (fanout_level_norep_kernel);
+edge_weight is dropped from the strategies, as the graphs here are weighted.
 """
 import argparse, json, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -35,11 +38,14 @@ ap.add_argument("--seed", type=int, default=42)
 ap.add_argument("--threads", type=int, default=16)
 ap.add_argument("--repeat", type=int, default=5)
 ap.add_argument("--no-host", action="store_true")
+ap.add_argument("--no-replace", action="store_true")
 args = ap.parse_args()
+replace = not args.no_replace
 
 gpu = grapehip.Engine(rank=0, world=1, master_port=29924,
                       n_threads=args.threads, gpu=True)
-strategies = args.strategies.split(",")
+strategies = [s for s in args.strategies.split(",")
+              if replace or s != "edge_weight"]
 workloads = []
 for spec in args.workloads.split(","):
     n, fan = spec.split("x")
@@ -48,7 +54,7 @@ for spec in args.workloads.split(","):
 
 def device_runs(g, seeds, fanouts, out):
     for st in strategies:
-        kw = dict(strategy=st, top_k=args.top_k, seed=7)
+        kw = dict(strategy=st, top_k=args.top_k, seed=7, replace=replace)
         r = gpu.sample_neighbors(g, seeds, fanouts, device=True, **kw)
         offs = r["level_offsets"]
         entry = {"draws": int(r["traversed_edges"]),
@@ -74,7 +80,8 @@ def host_runs(g, seeds, fanouts, out):
     for st in strategies:
         t0 = time.perf_counter()
         r = gpu.sample_neighbors(g, seeds[:n_host], fanouts, strategy=st,
-                                 top_k=args.top_k, seed=7, device=False)
+                                 top_k=args.top_k, seed=7, device=False,
+                                 replace=replace)
         secs = time.perf_counter() - t0
         draws = int((r["nodes"][:, 1:] >= 0).sum())
         e = out[st]
@@ -91,7 +98,7 @@ for scale in (int(x) for x in args.scales.split(",") if x):
         seeds = np.random.default_rng(args.seed).integers(
             0, nv, size=n, dtype=np.int64)
         out = {"graph": "rmat", "vertices": nv, "arcs": len(src), "seeds": n,
-               "fanouts": fanouts, "k": args.top_k}
+               "fanouts": fanouts, "k": args.top_k, "replace": replace}
         device_runs(g, seeds, fanouts, out)
         if not args.no_host:
             host_runs(g, seeds, fanouts, out)
@@ -107,7 +114,7 @@ for shape in (x for x in args.synthetic.split(",") if x):
             0, nv, size=n, dtype=np.int64)
         out = {"graph": "load_synthetic", "vertices": nv, "input_edges": ne,
                "stored_arcs": int(g.num_edges), "seeds": n,
-               "fanouts": fanouts, "k": args.top_k}
+               "fanouts": fanouts, "k": args.top_k, "replace": replace}
         device_runs(g, seeds, fanouts, out)
         print(json.dumps(out), flush=True)
     del g
